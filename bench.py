@@ -5,6 +5,12 @@
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts its own N rank processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --full [--no-cpu ...]                   (every side leg after the timed steps; full record in bench_full.json)
+    python bench.py --steps K --warmup W --dump-outputs DIR  (the last timed step's outputs as DIR/*.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = milliseconds per timed step,
+`dtype`, ...).  The side legs — bf16 and parity-grade repeats of the steps, PCIe-inclusive rate, per-kernel roofline, collate, table
+mode with its at-scale parity, small ops, CPU baseline with the oracle parity bridge, training step, drop-in — run with --full only.
 
 --config selects the BASELINE.json configuration (default 1, the one the metric is quoted on):
   1  CR-Module, MIND-small shape, bert-base-uncased architecture, bf16
@@ -92,7 +98,8 @@ def parse():
                    help="exit with status 3 (after the line has been printed) when any guarded side leg failed — for CI; the default "
                         "keeps status 0 so that a broken side leg never costs the driver its headline line (legs.errors names it)")
     p.add_argument("--no-parity-grade", action="store_true", help="skip the repeat of the timed steps in the parity-grade arithmetic (f16x3)")
-    p.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"), help="where the complete result (every leg) is written")
+    p.add_argument("--full-json", default=None, help="with --full: where the complete result (every leg) is written (default bench_full.json "
+                                                      "beside this file)")
     p.add_argument("--no-kernel-profile", action="store_true")
     p.add_argument("--no-collate", action="store_true", help="skip the device-side collate leg")
     p.add_argument("--no-table", action="store_true", help="skip the table-mode (encode pool once + all-gather) leg")
@@ -101,7 +108,20 @@ def parse():
     p.add_argument("--no-train", action="store_true", help="skip the training-step leg (SURVEY §8f-3)")
     p.add_argument("--no-dropin", action="store_true", help="skip the drop-in leg (mirror classes under the unchanged CRModule.forward at B = 8 / 64)")
     p.add_argument("--dropin-only", default="", help="profiling aid: run only this case of the drop-in leg, e.g. 8:train")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run every side leg after the timed steps (bf16 / parity-grade / PCIe-inclusive repeats, per-kernel roofline, "
+                        "collate, table mode, at-scale parity, small ops, CPU baseline, training step, drop-in) and write the full record; "
+                        "the --no-* switches above select among them.  Without it a run times the headline steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full_json is not None and not args.full:
+        p.error("--full-json needs --full: a plain run writes no record besides its line")
+    if args.full_json is None:
+        args.full_json = os.path.join(ROOT, "bench_full.json")
+    return args
 
 
 class StepBatch:
@@ -139,6 +159,27 @@ def run_step(encs, b, precision, chunk_tokens, table_bufs, plane_buf, weights):
         scores = hip.zscore_fuse(plane_buf[:, : b.n_cand], list(weights), b.cand_off)
     topk, ndcg = hip.rank_ndcg(scores, b.labels, b.cand_off, 10)
     return scores, topk, ndcg
+
+
+DUMP_TABLE_ROWS = 4096          # seeded sample of each module's [CLS] table in --dump-outputs (12.6 MB per module at H = 768)
+
+
+def dump_outputs(out_dir, last, tables, n_news):
+    """--dump-outputs: what run_step returned for the last timed step (ragged scores, top-10 positions, nDCG@10) and a fixed, seeded
+    row sample of every module's [CLS] table of that step, as .npy in float32 / float64 (top-10 positions: float64, exact)."""
+    scores, topk, ndcg = last
+    rows = np.sort(np.random.default_rng(0).choice(n_news, size=min(n_news, DUMP_TABLE_ROWS), replace=False))
+    rows_d = torch.from_numpy(rows).to(scores.device)
+    arrays = {"scores": scores.float().cpu().numpy(), "top10": topk.cpu().numpy().astype(np.float64), "ndcg10": ndcg.float().cpu().numpy(),
+              "table_rows": rows.astype(np.float64)}
+    for k, t in enumerate(tables):
+        arrays[f"table_m{k}"] = t[:n_news].index_select(0, rows_d).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir} ({total / 1e6:.1f} MB: {', '.join(sorted(arrays))})")
 
 
 # --------------------------------------------------------------------------------------------------- CPU baseline
@@ -1350,7 +1391,8 @@ def main():
     # reference's own `precision: 16-mixed`) is the headline because it is the one whose nDCG@10 stays within 1e-4 of the
     # fp32 parity mode on the whole dev-set shape; bf16 (BASELINE.json's wording for configs[1]) is timed right after it
     # on the same batches and reported as `bf16_mode`, with its own at-scale parity.
-    precs = tuple(dict.fromkeys(("bf16", "fp32", "f16", args.precision, PARITY_GRADE)))
+    # A plain run packs (and below, warms) the headline arithmetic only; the other modes serve the repeats of --full.
+    precs = tuple(dict.fromkeys(("bf16", "fp32", "f16", args.precision, PARITY_GRADE))) if args.full else (args.precision,)
     encs = [hip.HipEncoder(cfg, w, precisions=precs, device=dev) for w in weight_sets]
     n_news = conf["dims"]["n_news"]
     log(f"synthesising the {conf['shape']}-shaped news pool ({n_news} news) + impressions")
@@ -1375,7 +1417,7 @@ def main():
     # initialisation, not a step: every kernel variant the encoders can pick (16-bit and fp32 code objects, the tail-chunk and [CLS]
     # tail shapes) is launched once on a small slice of the pool so that no timed step pays a first-use code-object load
     init_n = min(2048, pool_ids.shape[0])
-    for prec in dict.fromkeys((args.precision, "bf16")):
+    for prec in dict.fromkeys((args.precision, "bf16") if args.full else (args.precision,)):
         for k in range(K):
             encs[k].encode_cls(pool_ids[:init_n], pool_mask[:init_n], precision=prec, host_lengths=pool_len[:init_n],
                                max_chunk_tokens=args.chunk_tokens, out=table_bufs[k][:init_n] if init_n <= max_news else None)
@@ -1398,8 +1440,11 @@ def main():
     for e in encs:
         e.status()
     hip.check_status(dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, table_bufs, batches[-1].ids.shape[0])
+    # everything below up to the line is a side leg: it runs with --full only
     elapsed_bf16 = None
-    if args.precision == "f16":                       # the same steps in bf16, same protocol
+    if args.full and args.precision == "f16":         # the same steps in bf16, same protocol
         run_step(encs, batches[0], "bf16", args.chunk_tokens, table_bufs, plane_buf, fuse_w)
         torch.cuda.synchronize()
         barrier()
@@ -1414,7 +1459,7 @@ def main():
     # ... and in the parity-grade arithmetic (f16x3: f32 activations, every GEMM as split f16 products — the fast mode whose top-10 lists
     # match the reference's): the SAME timed steps, same protocol, so the record carries an index-exact rate next to the headline
     elapsed_pg = None
-    if args.precision != PARITY_GRADE and PARITY_GRADE in precs and not args.no_parity_grade:
+    if args.full and args.precision != PARITY_GRADE and PARITY_GRADE in precs and not args.no_parity_grade:
         run_step(encs, batches[0], PARITY_GRADE, args.chunk_tokens, table_bufs, plane_buf, fuse_w)
         torch.cuda.synchronize()
         barrier()
@@ -1432,7 +1477,7 @@ def main():
     # the host, so this is what a caller pays who feeds host token tensors): ids + mask copied from pinned host memory
     # in front of every step, on the same stream
     pcie_s = None
-    if rank == 0:
+    if rank == 0 and args.full:
         host = [(b.ids.cpu().pin_memory(), b.mask.cpu().pin_memory()) for b in batches[args.warmup:]]
         torch.cuda.synchronize(); t0 = time.perf_counter()
         for b, (hi_, hm_) in zip(batches[args.warmup:], host):
@@ -1505,7 +1550,7 @@ def main():
                                            "steps": args.steps, "tag": "same timed steps, split-f16 GEMMs over f32 activations"}
 
     # per-kernel roofline: same steps again with every launch bracketed by HIP events on the launch stream
-    if rank == 0 and not args.no_kernel_profile:
+    if rank == 0 and args.full and not args.no_kernel_profile:
         log("per-kernel HIP-event pass")
         enc = encs[0]
         enc.profile(True)
@@ -1554,10 +1599,10 @@ def main():
             "avg_launch_us": kern[dom]["avg_us"], "flops_per_launch": kern[dom]["flops_per_launch"]}
     barrier()
 
-    if rank == 0 and not args.no_collate:
+    if rank == 0 and args.full and not args.no_collate:
         result["collate"] = guarded("collate leg", collate_leg, args, cfg, imp_all, pool_ids_np, pool_len, batches[-1], (n_steps - 1) * args.impressions, dev)
     del batches, table_bufs
-    if not args.no_table:
+    if args.full and not args.no_table:
         log("table mode")
         try:
             tab, par_scale, held = table_mode(args, conf, cfg, encs, fuse_w, (pool_ids, pool_mask, pool_len), rank, world, dev,
@@ -1600,10 +1645,10 @@ def main():
                                      "f16x3_what": "split-operand f16 GEMMs over f32 activations: within 1e-4 of the reference on the "
                                                    "goldens like the f32 mode; its ranking agreement with the f32 mode is in parity_at_scale"}
         del held
-    if rank == 0 and world == 1 and not args.no_small_ops:
+    if rank == 0 and world == 1 and args.full and not args.no_small_ops:
         log("small-kernel legs (pooler, dot, z-score, to_dense)")
         result["small_ops"] = guarded("small-kernel legs", small_ops_leg, dev)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         log("CPU baseline (oracle) + parity on the bounded sample")
         nb = max(2, args.cpu_impressions // K)
         args.parity_impressions = max(nb, args.parity_impressions // K // (4 if cfg.layers * cfg.hidden > 12 * 768 else 1))   # bounded CPU time
@@ -1612,19 +1657,23 @@ def main():
             result["cpu_baseline"], result["parity"] = got
         else:
             result["cpu_baseline"] = dict(got, value=None, unit="candidates/s", cores=None, kind="port", sample=None)
-    if rank == 0 and world == 1 and not args.no_train and cfg.head_dim == 64 and args.config == 1:
+    if rank == 0 and world == 1 and args.full and not args.no_train and cfg.head_dim == 64 and args.config == 1:
         log("training-step leg (train() mode encoder + scorer + SupCon + backward + AdamW)")
         # bf16 GEMM operands: f32's exponent range, so the step needs no loss scaling (f16 needs the caller's GradScaler, as the
         # reference's 16-mixed Lightning plugin provides — manner_amd/models/components/news_encoder.py train_precision)
         result["train_mode"] = guarded("training-step leg", train_leg, cfg, dev, args.precision if args.precision in ("bf16", "fp32") else "bf16")
-    if rank == 0 and world == 1 and not args.no_dropin and cfg.head_dim == 64 and args.config == 1:
+    if rank == 0 and world == 1 and args.full and not args.no_dropin and cfg.head_dim == 64 and args.config == 1:
         log("drop-in leg (mirror classes under the unchanged CRModule.forward, B = 8 and 64, eval + train)")
         for e in encs:
             e.close()
         result["dropin"] = guarded("drop-in leg", dropin_leg, cfg, model, weight_sets[0], (pool_ids, pool_mask, pool_len), dev,
                                    args.precision if args.precision in ("f16", "bf16", "fp32") else "f16", only=args.dropin_only)
     if rank == 0:
-        emit(result, args)
+        if args.full:
+            emit(result, args)
+        else:                                          # a plain run: the line alone, no side file
+            sys.stderr.flush()
+            print(compact_line(result), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
     if FAILED_LEGS:

@@ -123,16 +123,68 @@ def test_synthetic_inputs_are_deterministic_and_well_formed():
     assert np.array_equal(segment_ids(np.array([0, 2, 2, 5])), [0, 0, 2, 2, 2])
 
 
-REFERENCE = "/root/reference"          # exists in the build container only; the reference never travels to the GPU box
+def _classes(*names):
+    return "".join(f"\n\nclass {n}:\n    pass\n" for n in names)
+
+
+def _imports(*items):
+    return "".join(f"from {mod} import {name}" + (f" as {alias}" if alias else "") + "\n" for mod, name, alias in items)
+
+
+def _write_reference_layout(root):
+    """A stand-in for a checkout of the reference: its package layout and the module / class names that manner_amd.install() binds
+    into or must leave alone, with trivial class bodies written here.  The two caller modules import their operators
+    by path, as the reference's LightningModules do (cr_module.py:12-16, baselines/naml_plm_module.py:11-16); a components module
+    imports AdditiveAttention from the attention module, as the reference's news_encoder.py does.  One import line of each caller
+    reaches a module built on a third-party package (the loss on pytorch_metric_learning, a metric on torchmetrics), as in the
+    reference, so that a package this interpreter lacks is seen to be skipped as third-party rather than as a missing `manner`."""
+    comp = "manner.models.components"
+    files = {
+        "manner/__init__.py": "",
+        "manner/utils/__init__.py": "",
+        "manner/data/__init__.py": "",
+        "manner/data/components/__init__.py": "",
+        "manner/data/components/mind_batch.py": _classes("MINDRecBatch"),
+        "manner/models/__init__.py": "",
+        "manner/models/components/__init__.py": "",
+        "manner/models/components/attention.py": _classes("AdditiveAttention", "PolyAttention", "TargetAwareAttention", "DenseAttention"),
+        "manner/models/components/click_predictors.py": _classes("DotProduct"),
+        "manner/models/components/losses.py": "import pytorch_metric_learning\n" + _classes("SupConLoss"),
+        "manner/metrics/__init__.py": "",
+        "manner/metrics/diversity.py": "import torchmetrics\n" + _classes("Diversity"),
+        "manner/models/components/news_encoder.py": _imports((f"{comp}.attention", "AdditiveAttention", None)) + _classes(
+            "MannerTextEncoder", "MannerEntityEncoder", "MannerNewsEncoder", "PLMTextEncoder", "NAMLNewsEncoder", "LSTURNewsEncoder",
+            "MINERNewsEncoder", "CAUMNewsEncoder"),
+        "manner/models/components/user_encoder.py": _imports((f"{comp}.attention", "AdditiveAttention", None),
+                                                             (f"{comp}.attention", "DenseAttention", None)) + _classes(
+            "NAMLUserEncoder", "NRMSUserEncoder", "LSTURUserEncoder", "CAUMUserEncoder", "MINSUserEncoder"),
+        "manner/models/cr_module.py": _imports(("manner.data.components.mind_batch", "MINDRecBatch", None),
+                                               (f"{comp}.click_predictors", "DotProduct", None),
+                                               (f"{comp}.losses", "SupConLoss", None),
+                                               (f"{comp}.news_encoder", "MannerNewsEncoder", None),
+                                               (f"{comp}.user_encoder", "NAMLUserEncoder", "UserEncoder")) + _classes("CRModule"),
+        "manner/models/baselines/naml_plm_module.py": _imports(("manner.data.components.mind_batch", "MINDRecBatch", None),
+                                                               ("manner.metrics.diversity", "Diversity", None),
+                                                               (f"{comp}.click_predictors", "DotProduct", None),
+                                                               (f"{comp}.news_encoder", "NAMLNewsEncoder", "NewsEncoder"),
+                                                               (f"{comp}.user_encoder", "NAMLUserEncoder", "UserEncoder")) + _classes("NAMLPLMModule"),
+    }
+    for rel, text in files.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+    return root
+
 
 _INSTALL_SCRIPT = r'''
 import importlib.util, json, re, sys
 import manner_amd
 ref = sys.argv[1]
 early = "--early" in sys.argv
-def lines(path, a, b):                          # the reference's OWN import lines, read where they lie (nothing is copied into the repo)
+def lines(path):                                 # the caller module's own `from manner.… import …` lines, read where they lie
     with open(path) as f:
-        return [l.rstrip("\n") for l in f.readlines()[a - 1:b]]
+        return [l.rstrip("\n") for l in f if l.startswith("from manner.")]
 if early:                                        # a reference module imported BEFORE install(): its aliases must be rebound too
     sys.path.insert(0, ref)
     import manner.models.components.user_encoder as UE0
@@ -144,8 +196,10 @@ if early:                                        # a reference module imported B
 report = manner_amd.install(ref)
 out = {"report": report, "skipped_third_party": []}
 ns_cr, ns_naml = {}, {}
-for ns, path, a, b in ((ns_cr, ref + "/manner/models/cr_module.py", 12, 16), (ns_naml, ref + "/manner/models/baselines/naml_plm_module.py", 11, 16)):
-    for l in lines(path, a, b):
+for ns, path in ((ns_cr, ref + "/manner/models/cr_module.py"), (ns_naml, ref + "/manner/models/baselines/naml_plm_module.py")):
+    src = lines(path)
+    assert len(src) >= 4, (path, src)
+    for l in src:
         assert re.match(r"from manner\.[\w.]+ import ", l), l
         try:
             exec(l, ns)
@@ -173,20 +227,21 @@ print("RESULT " + json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference checkout exists in the build container only")
 @pytest.mark.parametrize("early", [False, True])
-def test_install_binds_the_mirror_into_the_real_reference_tree(early):
-    """VERDICT r3 item 2 — the binding must COEXIST with the reference tree.  In a fresh interpreter with this repository and the
-    reference checkout importable, after ``manner_amd.install()`` the exact import lines of reference manner/models/cr_module.py:12-16
-    give the mirror classes, those of baselines/naml_plm_module.py:11-16 give the mirror ``DotProduct`` / ``NAMLUserEncoder`` and the
-    REFERENCE's own ``NAMLNewsEncoder``; ``manner``, ``manner.utils``, ``manner.data``, ``manner.models.cr_module`` still resolve to the
-    reference's files; the untouched encoders / attentions stay the reference's classes, and the reference's ``NAMLNewsEncoder`` keeps
-    using the reference's ``AdditiveAttention``.  ``early``: a reference module imported before ``install()`` has its aliases rebound."""
+def test_install_binds_the_mirror_into_the_real_reference_tree(early, tmp_path):
+    """VERDICT r3 item 2 — the binding must COEXIST with the reference tree.  In a fresh interpreter with this repository and a
+    reference-layout tree importable (``_write_reference_layout``: the reference's packages, modules and class names, nothing of
+    its code), after ``manner_amd.install()`` the import lines of manner/models/cr_module.py give the mirror classes, those of
+    baselines/naml_plm_module.py give the mirror ``DotProduct`` / ``NAMLUserEncoder`` and the REFERENCE's own ``NAMLNewsEncoder``;
+    ``manner``, ``manner.utils``, ``manner.data``, ``manner.models.cr_module`` still resolve to the reference tree's files; the
+    untouched encoders / attentions stay the reference's classes, and the reference's ``NAMLNewsEncoder`` keeps using the reference's
+    ``AdditiveAttention``.  ``early``: a reference module imported before ``install()`` has its aliases rebound."""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    reference = _write_reference_layout(str(tmp_path / "reference"))
     env = dict(os.environ, PYTHONPATH=root, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", _INSTALL_SCRIPT, REFERENCE] + (["--early"] if early else []), env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "-c", _INSTALL_SCRIPT, reference] + (["--early"] if early else []), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
     mir = "manner_amd.models.components."
@@ -198,10 +253,14 @@ def test_install_binds_the_mirror_into_the_real_reference_tree(early):
     assert out["naml_plm_module"]["DotProduct"] == mir + "click_predictors.DotProduct"
     assert out["naml_plm_module"]["UserEncoder"] == mir + "user_encoder.NAMLUserEncoder"
     for k in ("manner_file", "utils_origin", "data_origin", "cr_module_origin"):
-        assert out[k].startswith(REFERENCE + "/manner/"), (k, out[k])
+        assert out[k].startswith(reference + "/manner/"), (k, out[k])
     assert all(v.startswith("manner.models.components.") for v in out["kept"].values()), out["kept"]
     assert out["naml_inner_additive"] == "manner.models.components.attention.AdditiveAttention"
     assert all(e[1].split(".")[0] in ("pytorch_metric_learning", "torchmetrics", "lightning", "torch_geometric") for e in out["skipped_third_party"]), out["skipped_third_party"]
+    import importlib.util
+    missing = sorted(m for m in ("pytorch_metric_learning", "torchmetrics") if importlib.util.find_spec(m) is None)
+    assert sorted(e[1] for e in out["skipped_third_party"]) == missing, (out["skipped_third_party"], missing)
+    assert ("SupConLoss" in out["cr_module"]) == ("pytorch_metric_learning" not in missing)
     assert out["ue_keys"] == ["additive_attention.linear.bias", "additive_attention.linear.weight", "additive_attention.query"]
     assert out["after_uninstall"] == "manner.models.components.news_encoder.MannerNewsEncoder"
     assert sorted(out["report"]["manner.models.components.news_encoder"]) == ["MannerEntityEncoder", "MannerNewsEncoder", "MannerTextEncoder", "PLMTextEncoder"]
@@ -693,6 +752,44 @@ def test_bench_final_line_is_compact_strict_json(tmp_path, capsys):
     line2 = bench.compact_line(result)
     j2 = json.loads(line2, parse_constant=reject)
     assert len(line2.encode()) < 8192 and {"config", "roofline", "cpu_baseline"} <= set(j2) and "kernel_avg_us" not in j2.get("legs", {})
+
+
+def test_bench_plain_run_and_output_dump(tmp_path, monkeypatch):
+    """bench.py parses `--full` (the side legs) off by default, refuses `--full-json` without it, validates `--steps`, and
+    `--dump-outputs` writes the last step's scores / top-10 / nDCG and a seeded [CLS]-table row sample as float32 /
+    float64 .npy files below 64 MB — the same files for the same step."""
+    bench = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path) and a.full_json == os.path.join(bench.ROOT, "bench_full.json")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full-json", str(tmp_path / "r.json")])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    g = torch.Generator().manual_seed(5)
+    n_news, n_cand, nb = 5000, 300, 12
+    last = (torch.randn(n_cand, generator=g), torch.randint(-1, 40, (nb, 10), generator=g, dtype=torch.int32), torch.rand(nb, generator=g))
+    tables = [torch.randn(n_news + 17, 16, generator=g) for _ in range(2)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), last, tables, n_news)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["ndcg10.npy", "scores.npy", "table_m0.npy", "table_m1.npy", "table_rows.npy", "top10.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    rows = np.load(tmp_path / "a" / "table_rows.npy").astype(np.int64)
+    assert len(rows) == bench.DUMP_TABLE_ROWS and (np.diff(rows) > 0).all() and rows.max() < n_news
+    assert np.array_equal(np.load(tmp_path / "a" / "table_m1.npy"), tables[1][torch.from_numpy(rows)].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "top10.npy"), last[1].numpy().astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), last[0].numpy())
 
 
 def test_segment_offsets_without_a_host_read():

@@ -1,4 +1,4 @@
-F="--gpus 1 --steps 2 --warmup 1 --no-cpu --no-table --no-small-ops --no-collate --no-train --no-kernel-profile --no-parity-grade --dropin-only 8:eval"
+F="--full --gpus 1 --steps 2 --warmup 1 --no-cpu --no-table --no-small-ops --no-collate --no-train --no-kernel-profile --no-parity-grade --dropin-only 8:eval"
 for i in 1 2 3; do
 for m in 256 auto; do
   if [ $m = auto ]; then unset MANNER_HIP_GEMM_PANEL; else export MANNER_HIP_GEMM_PANEL=$m; fi

@@ -5,7 +5,7 @@ set -u
 VAR="$1"; REPS="$2"; shift 2
 O=gpurun_out/r6
 mkdir -p "$O"
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu --no-table --no-collate --no-small-ops --no-train --no-dropin --no-scale-parity --no-parity-grade"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-table --no-collate --no-small-ops --no-train --no-dropin --no-scale-parity --no-parity-grade"
 for rep in $(seq 1 "$REPS"); do
   for v in "$@"; do
     F="$O/abm_${VAR}_${v}_rep${rep}"

@@ -6,7 +6,7 @@ set -u
 VAR="$1"; A="$2"; BV="$3"; REPS="${4:-2}"
 O=gpurun_out/r6
 mkdir -p "$O"
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu --no-table --no-collate --no-small-ops --no-train --no-dropin --no-scale-parity --no-parity-grade"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-table --no-collate --no-small-ops --no-train --no-dropin --no-scale-parity --no-parity-grade"
 for rep in $(seq 1 "$REPS"); do
   for v in "$A" "$BV"; do
     F="$O/ab_${VAR}_${v}_rep${rep}"

@@ -4,7 +4,7 @@
 # Cache between producer and consumer), with the socket power and clocks sampled during every run.  Raw output:
 # gpurun_out/r3/ab_*.json / ab_*.smi; summary: profiles/r3/ab_chunk_nt.md (tools/collect_r3.py).
 mkdir -p gpurun_out/r3
-F="--steps 10 --warmup 2 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-train --no-dropin --no-kernel-profile"
+F="--full --steps 10 --warmup 2 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-train --no-dropin --no-kernel-profile"
 for ct in 65536 32768 16384; do
   for nt in 1 0; do
     tag="ct${ct}_nt${nt}"

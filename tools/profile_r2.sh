@@ -5,7 +5,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 O=gpurun_out/prof_r2
 rm -rf $O && mkdir -p $O
-B="python3 bench.py --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops"
+B="python3 bench.py --full --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops"
 # 1. per-kernel durations, single stream so that launch durations are not inflated by the second stream
 MANNER_HIP_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 3 > $O/stats.log 2>&1
 echo "stats done"

@@ -5,7 +5,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 O=gpurun_out/prof_r3
 rm -rf $O && mkdir -p $O
-B="python3 bench.py --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops --no-train --no-dropin"
+B="python3 bench.py --full --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops --no-train --no-dropin"
 # 1. per-kernel durations of the headline steps, single stream so that launch durations are not inflated by the second stream
 MANNER_HIP_STREAMS=1 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 3 > $O/stats.log 2>&1
 echo "stats done"
@@ -23,7 +23,7 @@ timeout -k 10 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv 
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/tail_write -- python3 tools/tail_probe.py > /dev/null 2> $O/tail_write.log
 echo "tail done"
 # 5. the training-step leg alone, ONE stream (no inference kernels measured under a concurrent stream)
-T="python3 bench.py --steps 1 --warmup 0 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-kernel-profile --no-dropin"
+T="python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-kernel-profile --no-dropin"
 MANNER_HIP_STREAMS=1 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -- $T > $O/train.log 2>&1
 echo "train done"
 # keep only what the collectors need: the big per-dispatch CSVs stay on the box except the counter / stats tables

@@ -9,7 +9,7 @@ O="$R/gpurun_out/prof_r4"
 rm -rf "$O" && mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 export MANNER_HIP_STREAMS=1        # single stream: launch durations are not inflated by the second stream
-B="python3 $R/bench.py --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops --no-train --no-dropin"
+B="python3 $R/bench.py --full --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops --no-train --no-dropin"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- $B --steps 3 > "$O/stats.log" 2>&1; echo "stats done"
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -- $B --steps 1 > "$O/fetch.log" 2>&1; echo "fetch done"
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/write" -- $B --steps 1 > "$O/write.log" 2>&1; echo "write done"
@@ -21,6 +21,6 @@ timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv 
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/tail_write" -- python3 "$R/tools/tail_probe.py" > /dev/null 2> "$O/tail_write.log"; echo "tail write done"
 # the training-step leg alone, ONE stream
 export MANNER_HIP_STREAMS=1
-timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/train" -- python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-kernel-profile --no-dropin > "$O/train.log" 2>&1; echo "train done"
+timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/train" -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-kernel-profile --no-dropin > "$O/train.log" 2>&1; echo "train done"
 find "$O" -name "*kernel_trace.csv" -size +4M -delete
 du -sh "$O"

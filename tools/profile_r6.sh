@@ -9,7 +9,7 @@ O="$R/gpurun_out/prof_r6"
 rm -rf "$O" && mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 export MANNER_HIP_STREAMS=1        # single stream: launch durations are not inflated by the second stream
-B="python3 $R/bench.py --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops --no-train --no-dropin --no-parity-grade"
+B="python3 $R/bench.py --full --warmup 1 --no-cpu --no-kernel-profile --no-table --no-collate --no-small-ops --no-train --no-dropin --no-parity-grade"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- $B --steps 3 > "$O/stats.log" 2>&1; echo "stats done"
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -- $B --steps 1 > "$O/fetch.log" 2>&1; echo "fetch done"
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/write" -- $B --steps 1 > "$O/write.log" 2>&1; echo "write done"

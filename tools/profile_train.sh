@@ -2,7 +2,7 @@
 # training-step leg alone under rocprofv3 --kernel-trace --stats (round 2)
 set -e
 mkdir -p gpurun_out/r2/train_prof
-F="--steps 1 --warmup 0 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-kernel-profile"
+F="--full --steps 1 --warmup 0 --no-cpu --no-table --no-scale-parity --no-small-ops --no-collate --no-kernel-profile"
 python bench.py $F > gpurun_out/r2/train_bench.json 2> gpurun_out/r2/train_bench.err
 python - <<'PY'
 import json
