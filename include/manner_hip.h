@@ -40,7 +40,8 @@ enum {
  * (the encoder handle's own, or the caller-owned int32 `status` argument of the scoring entry points, which may be
  * NULL) and continue on a safe substitute.  The reference raises a Python exception in each of these cases. */
 enum {
-  MANNER_HIP_STATUS_MASK = 1,     /* attention_mask is not a right-padded 0/1 prefix with 1..MAX_LEN tokens */
+  MANNER_HIP_STATUS_MASK = 1,     /* attention_mask is not a right-padded 0/1 prefix with 1..MAX_LEN_INFER tokens (inference) or
+                                     1..MAX_LEN tokens (training) */
   MANNER_HIP_STATUS_TOKEN = 2,    /* input id / position outside the embedding tables (IndexError in the reference) */
   MANNER_HIP_STATUS_FUSED = 4,    /* reserved (bounded-wait overflow of a fused kernel) */
   MANNER_HIP_STATUS_INDEX = 8,    /* news / entity index outside the table (IndexError in the reference) */
@@ -122,7 +123,10 @@ size_t manner_hip_encoder_workspace_bytes(manner_hip_encoder_t enc, int64_t max_
  *   ids, mask : int64 [n_news, padded_len] row-major, exactly the tensors of the reference's
  *               BatchEncoding (manner/data/components/mind_rec_dataset.py:134-137); `mask` must be
  *               a right-padded 0/1 prefix mask with >= 1 real token per news (validated on device,
- *               see manner_hip_encoder_status);
+ *               see manner_hip_encoder_status); padded_len <= MANNER_HIP_MAX_LEN_INFER (512), and every news
+ *               also within its model's position table (a longer row raises MANNER_HIP_STATUS_TOKEN, the
+ *               reference's IndexError).  Rows of <= MANNER_HIP_MAX_LEN (128) tokens run the short-row kernels
+ *               whatever the padded length or their neighbours; longer rows take the long-row attention;
  *   host_lengths : optional host int32 [n_news] copy of the row sums of `mask`.  With it the
  *               launch grids are exact; without it (NULL) grids cover n_news*padded_len tokens
  *               and surplus workgroups exit early.  No host synchronisation either way.  The lengths only
@@ -144,7 +148,8 @@ int manner_hip_encode_cls(manner_hip_encoder_t enc, const int64_t* ids, const in
  * be cached per news — provided the embedding tables, which that name test does not freeze, are
  * not trained either.  Arguments as manner_hip_encode_cls; out [n_news, padded_len, H] of
  * out_dtype (0 = f32, 1 = bf16).  Rows of padded positions are written as zeros: HF computes throw-away values there
- * which never reach a real token (keys are masked) — feed the tensor with the same attention_mask. */
+ * which never reach a real token (keys are masked) — feed the tensor with the same attention_mask.  padded_len up to
+ * MANNER_HIP_MAX_LEN_INFER, as manner_hip_encode_cls. */
 int manner_hip_encode_hidden(manner_hip_encoder_t enc, const int64_t* input_ids, const int64_t* attention_mask,
                              const int32_t* host_lengths, int64_t n_news, int64_t padded_len, int32_t precision,
                              int32_t n_layers, int32_t out_dtype, void* out, void* workspace, size_t workspace_bytes,
@@ -152,13 +157,17 @@ int manner_hip_encode_hidden(manner_hip_encoder_t enc, const int64_t* input_ids,
 
 /* Blocking: synchronises `stream` and returns MANNER_HIP_E_INPUT if any encode_cls call on this
  * handle since the last status call saw an invalid mask (non-prefix, empty or longer than
- * MANNER_HIP_MAX_LEN); clears the flag. */
+ * MANNER_HIP_MAX_LEN_INFER) or token / position index; clears the flag. */
 int manner_hip_encoder_status(manner_hip_encoder_t enc, manner_hip_stream_t stream);
 /* Non-blocking form: enqueues a copy of the flag word into `host_flag` (pinned host int32) followed by its reset,
  * both on `stream`; the caller reads *host_flag once an event recorded after this call has completed.  This is how
  * the module mirror surfaces bad inputs of call k at call k+1 without a host synchronisation per forward. */
 int manner_hip_encoder_status_async(manner_hip_encoder_t enc, int32_t* host_flag /*pinned host*/, manner_hip_stream_t stream);
+/* Per-row token limits.  MANNER_HIP_MAX_LEN: the training path (manner_hip_encode_full, the train_* entry points) and the
+ * short-row attention tile (at most four 32-key tiles per wave).  MANNER_HIP_MAX_LEN_INFER: the inference entry points
+ * manner_hip_encode_cls / manner_hip_encode_hidden, whose rows of 129..512 tokens run the long-row attention kernels. */
 #define MANNER_HIP_MAX_LEN 128
+#define MANNER_HIP_MAX_LEN_INFER 512
 
 /* ABI v8 — sampled fingerprint of a set of tensors, for hosts that cache copies of caller-owned parameters (the module mirror's
  * inference handle packs the PLM weights once; torch's version counters do not see a write through `p.data`).  out[i] = a 32-bit

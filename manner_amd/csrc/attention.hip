@@ -1,7 +1,10 @@
 // K3: bidirectional multi-head self-attention over packed variable-length news
 // (HF BertSelfAttention / eager_attention_forward, transformers/models/bert/modeling_bert.py:111-136,
 // 188-203; additive padding mask of :704-708).  Tokens are packed, so the padding mask becomes
-// "keys of the same news only"; head_dim is 64 and a news has at most 128 tokens (<= 4 key tiles).
+// "keys of the same news only"; head_dim is 64.  A news of at most 128 tokens (MANNER_HIP_MAX_LEN, <= 4 key tiles) runs the
+// one-wave-per-(news, head) kernels below whatever the call's padded length; a news of 129..512 tokens (inference only) runs
+// the long-row kernels (attn_long16_kernel, attn_long_f32_kernel), launched next to them over the same rows — each kernel
+// returns at once for the rows of the other, so the bits of a short row never depend on the padded length or its neighbours.
 //
 // bf16 path — one 64-lane wave per (news, head), no workgroup barriers:
 //   memory    every global access is a 16-byte piece of a whole 128-byte row segment (8 lanes per row): K tiles and
@@ -208,6 +211,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const TE* __restrict_
   const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
   const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
+  if (L > MANNER_HIP_MAX_LEN) return;                // wave-uniform: a long row (attn_long16_kernel)
   char* vl = vlds + wave * lds_per_wave;
   if (L <= 32) attn_wave_bf16<TE, 1>(qkv, ctx, tok0, L, H, head, vl);
   else if (L <= 64) attn_wave_bf16<TE, 2>(qkv, ctx, tok0, L, H, head, vl);
@@ -557,7 +561,7 @@ __global__ __launch_bounds__(128, 1) void attn_x3_kernel(const float* __restrict
   const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
   const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
-  if (L <= 0) return;
+  if (L <= 0 || L > MANNER_HIP_MAX_LEN) return;     // a long row: attn_long_f32_kernel
   char* vl = vlds + wave * lds_per_wave;
   if (NKTMAX == 1 || L <= 32) attn_wave_x3<1>(qkv, tok0, L, H, head, vl, a3);
   else if (NKTMAX == 2 || L <= 64) { if constexpr (NKTMAX >= 2) attn_wave_x3<2>(qkv, tok0, L, H, head, vl, a3); }
@@ -575,6 +579,7 @@ __global__ __launch_bounds__(128, 1) void attn_f32_mfma_kernel(const float* __re
   const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
   const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
+  if (L > MANNER_HIP_MAX_LEN) return;                // a long row: attn_long_f32_kernel
   char* vl = vlds + wave * lds_per_wave;
   if (L <= 32) attn_wave_f32<1>(qkv, ctx, tok0, L, H, head, vl, a3, a3_dt);
   else if (L <= 64) attn_wave_f32<2>(qkv, ctx, tok0, L, H, head, vl, a3, a3_dt);
@@ -589,6 +594,7 @@ __global__ __launch_bounds__(128) void attn_f32_kernel(const float* __restrict__
   __shared__ __attribute__((aligned(16))) float Vs[MANNER_HIP_MAX_LEN * 64];
   const int n = blockIdx.x / heads, head = blockIdx.x - n * heads;
   const int tok0 = cu[n], L = cu[n + 1] - tok0;
+  if (L > MANNER_HIP_MAX_LEN) return;                // a long row: attn_long_f32_kernel (the images below hold 128 rows)
   const size_t ld = 3 * (size_t)H;
   const float* Qb = qkv + (size_t)tok0 * ld + head * 64;
   for (int i = threadIdx.x; i < L * 16; i += 128) {
@@ -629,6 +635,298 @@ __global__ __launch_bounds__(128) void attn_f32_kernel(const float* __restrict__
 #pragma unroll
   for (int c = 0; c < 64; c += 4)
     *reinterpret_cast<f32x4*>(dst + c) = f32x4{o[c] * inv, o[c + 1] * inv, o[c + 2] * inv, o[c + 3] * inv};
+}
+
+// ---- long rows (MANNER_HIP_MAX_LEN < L <= MANNER_HIP_MAX_LEN_INFER, inference only), 16-bit: flash-style, one workgroup of
+// LONG16_WAVES waves per (news, head, block of 32 LONG16_WAVES queries), each wave owning 32 queries exactly as attn_wave_bf16 does
+// (S^T = K Q^T with the query on the lane, online softmax over 32-key tiles in f32, the S^T accumulators converted pairwise as the B
+// operand of O^T = V^T P^T, V read key-permuted and transposed with ds_read_b64_tr_b16, O^T out through a wave-private slab as whole
+// 128-byte row segments).
+//   LDS: the WHOLE K and V of the (news, head) are staged once per workgroup, by LDS-DMA (no registers), before one barrier: at head
+//   dim 64 and 16-bit elements a 512-token row is 64 KiB of K + 64 KiB of V, which with the eight 4 KiB output slabs is 160 KiB —
+//   the CU's whole LDS.  A double-buffered 64-key stream would need 2 x 16 KiB and two more workgroups per CU, but one barrier per
+//   key tile; staging the row needs one barrier per workgroup and no pipeline, and a 512-token row is only two workgroups per
+//   (news, head), so K and V leave HBM once per workgroup and come from L2 for the second.  The dynamic LDS is sized by the call's
+//   padded length (rows_cap = padded length rounded up to 32): 96 KiB at 256 tokens.
+//   K image: row-major 128-byte rows, 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7) (the short kernel's slab swizzle; the DMA
+//   writes lane-linear, so each lane fetches the source chunk that belongs at its destination).  V image: plain row-major, as the
+//   short kernel's.  Rows >= L of the last tile replicate row L-1 (finite; masked / weighted by 0).
+constexpr int LONG16_WAVES = 8;
+
+template <typename TE>
+__global__ __launch_bounds__(64 * LONG16_WAVES, 1) void attn_long16_kernel(const TE* __restrict__ qkv, TE* __restrict__ ctx,
+                                                                           const int32_t* __restrict__ cu, int64_t n_pairs, int n_qb,
+                                                                           int heads, int H, int rows_cap) {
+  typedef typename E16<TE>::v8 e16x8;
+  typedef typename E16<TE>::v4 e16x4;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int64_t pair = (int64_t)blockIdx.x / n_qb;
+  const int qb = (int)((int64_t)blockIdx.x - pair * n_qb);
+  if (pair >= n_pairs) return;
+  const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
+  const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
+  const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
+  if (L <= MANNER_HIP_MAX_LEN || 32 * LONG16_WAVES * qb >= L) return;   // workgroup-uniform: a short row (attn_bf16_kernel) / past the row
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
+  const int r8 = lane >> 3, c8 = lane & 7;
+  char* kimg = lds;
+  char* vimg = lds + (size_t)rows_cap * 128;
+  char* ol = lds + (size_t)rows_cap * 256 + wave * 4096;
+  const size_t ld = 3 * (size_t)H;
+  const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
+  const TE* Kb = Qb + H;
+  const TE* Vb = Qb + 2 * H;
+  const int nrows = (L + 31) & ~31;
+  const int q0 = 32 * LONG16_WAVES * qb + 32 * wave;
+  // this wave's 32 query rows to registers first, then K and V of the whole row by LDS-DMA (8 rows x 128 B per instruction)
+  f32x4 qt[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = min(q0 + 8 * i + r8, L - 1);
+    qt[i] = *reinterpret_cast<const f32x4*>(Qb + (size_t)row * ld + 8 * (c8 ^ (((8 * i + r8) >> 1) & 7)));
+  }
+  for (int r0 = 8 * wave; r0 < nrows; r0 += 8 * LONG16_WAVES) {
+    const int row = min(r0 + r8, L - 1);
+    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(Kb + (size_t)row * ld + 8 * (c8 ^ (((r0 + r8) >> 1) & 7))), LDS_PTR(kimg + r0 * 128), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(Vb + (size_t)row * ld + 8 * c8), LDS_PTR(vimg + r0 * 128), 16, 0, 0);
+  }
+  // Q block: rows -> slab, chunk-swizzled -> fragments (attn_wave_bf16)
+  e16x8 qf[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(ol + (8 * i + r8) * 128 + (c8 << 4)) = qt[i];
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+    qf[ks] = *reinterpret_cast<const e16x8*>(ol + rr * 128 + (((2 * ks + h) ^ ((rr >> 1) & 7)) << 4));
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the K / V images (LDS-DMA is not tracked by the compiler)
+  __syncthreads();                                      // ... and every other wave's
+  if (q0 >= L) return;                                  // wave-uniform: no query of this wave is real (no barrier follows)
+
+  const int gi = lane & 15;
+  const int tr_base = ((gi >> 2) * 64 + 16 * ((lane >> 4) & 1) + 4 * (gi & 3)) * 2 + (4 * h) * 128;
+  constexpr float C = 0.125f * 1.44269504088896340736f;   // head_dim^-0.5 * log2(e)
+  float m = -INFINITY, l = 0.f;
+  f32x16 o[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+  const int nkt = nrows >> 5;
+  for (int kt = 0; kt < nkt; ++kt) {
+    e16x8 kf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      kf[ks] = *reinterpret_cast<const e16x8*>(kimg + (32 * kt + rr) * 128 + (((2 * ks + h) ^ ((rr >> 1) & 7)) << 4));
+    f32x16 st;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) st = E16<TE>::mfma32(kf[ks], qf[ks], st);
+    if (32 * kt + 32 > L) {                             // wave-uniform: the last tile holds keys >= L
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = 32 * kt + (e & 3) + 8 * (e >> 2) + 4 * h;
+        st[e] = key < L ? st[e] : -INFINITY;
+      }
+    }
+    float tmx = fmaxf(fmaxf(fmaxf(st[0], st[1]), fmaxf(st[2], st[3])), fmaxf(fmaxf(st[4], st[5]), fmaxf(st[6], st[7])));
+    tmx = fmaxf(tmx, fmaxf(fmaxf(fmaxf(st[8], st[9]), fmaxf(st[10], st[11])), fmaxf(fmaxf(st[12], st[13]), fmaxf(st[14], st[15]))));
+    tmx = fmaxf(tmx, __shfl_xor(tmx, 32, 64));
+    const float mn = fmaxf(m, tmx);                     // finite: tile 0 always holds key 0 < L
+    const float nmc = -mn * C;
+    float rs = 0.f;
+    e16x8 pf[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float p = __builtin_amdgcn_exp2f(fmaf(st[e], C, nmc));   // exp((s - max) / 8); 0 for masked keys
+      pf[e >> 3][e & 7] = (TE)p;
+      rs += p;
+    }
+    rs += __shfl_xor(rs, 32, 64);
+    if (kt == 0) {
+      l = rs;
+    } else {
+      const float alpha = __builtin_amdgcn_exp2f((m - mn) * C);
+      l = l * alpha + rs;
+      if (__any(mn > m)) {                              // wave-uniform: some query's running max moved
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) o[dt][e] *= alpha;
+      }
+    }
+    m = mn;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const char* a0 = vimg + tr_base + (32 * kt + 16 * s2) * 128 + (32 * dt) * 2;
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 8 * 128));
+        typedef short s16x8 __attribute__((ext_vector_type(8)));
+        const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        o[dt] = E16<TE>::mfma32(__builtin_bit_cast(e16x8, both), pf[s2], o[dt]);
+      }
+    }
+  }
+  // O^T -> ctx rows through the wave's slab (attn_wave_bf16)
+  const float inv = 1.0f / l;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c = 4 * dt + g;
+      *reinterpret_cast<e16x4*>(ol + rr * 128 + ((c ^ ((rr >> 1) & 7)) << 4) + 8 * h) =
+          e16x4{(TE)(o[dt][4 * g] * inv), (TE)(o[dt][4 * g + 1] * inv), (TE)(o[dt][4 * g + 2] * inv), (TE)(o[dt][4 * g + 3] * inv)};
+    }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 8 * i + r8;
+    const int q = q0 + row;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(ol + row * 128 + (c8 << 4));
+    if (q < L) *reinterpret_cast<f32x4*>(ctx + (size_t)(tok0 + q) * H + head * 64 + 8 * (c8 ^ ((row >> 1) & 7))) = v;
+  }
+}
+
+// ---- long rows, exact f32 (fp32 / f16x3 / bf16x3 modes): the arithmetic of attn_wave_f32 (v_mfma_f32_32x32x2_f32, scores / 8, expf,
+// online softmax over 32-key tiles) in a workgroup of LONGF_WAVES waves per (news, head, block of 32 LONGF_WAVES queries).  f32 K and
+// V of a 512-token row are 256 KiB, beyond the LDS: they are streamed through it in chunks of LONGF_KC keys (32 KiB of K + 32 KiB of
+// V, by LDS-DMA, shared by all waves; two barriers per chunk), the K image chunk-swizzled with row & 15 as attn_wave_f32's slab.
+// a3 != NULL: the rows are written as the out-projection's split operand [hi | hi | lo] (as attn_wave_f32).  Judged on accuracy.
+constexpr int LONGF_WAVES = 4, LONGF_KC = 128;
+constexpr int LONGF_LDS = 2 * LONGF_KC * 256 + LONGF_WAVES * 8192;
+
+__global__ __launch_bounds__(64 * LONGF_WAVES, 1) void attn_long_f32_kernel(const float* __restrict__ qkv, float* __restrict__ ctx,
+                                                                            const int32_t* __restrict__ cu, int64_t n_pairs, int n_qb,
+                                                                            int heads, int H, void* __restrict__ a3, int a3_dt) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int64_t pair = (int64_t)blockIdx.x / n_qb;
+  const int qb = (int)((int64_t)blockIdx.x - pair * n_qb);
+  if (pair >= n_pairs) return;
+  const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
+  const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
+  const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
+  if (L <= MANNER_HIP_MAX_LEN || 32 * LONGF_WAVES * qb >= L) return;     // workgroup-uniform
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
+  const int r4 = lane >> 4, c16 = lane & 15;
+  char* kimg = lds;
+  char* vimg = lds + LONGF_KC * 256;
+  char* ol = lds + 2 * LONGF_KC * 256 + wave * 8192;
+  const size_t ld = 3 * (size_t)H;
+  const float* Qb = qkv + (size_t)tok0 * ld + head * 64;
+  const float* Kb = Qb + H;
+  const float* Vb = Qb + 2 * H;
+  const int q0 = 32 * LONGF_WAVES * qb + 32 * wave;
+  const bool active = q0 < L;                           // wave-uniform; an idle wave still takes part in the chunk loads and barriers
+  // Q block -> slab (16-byte chunks XOR-swizzled with row & 15) -> lane (rr, h) takes the 32 features 32h .. 32h+31 of query rr
+  float qf[32];
+  {
+    f32x4 t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = min(q0 + 4 * i + r4, L - 1);
+      t[i] = *reinterpret_cast<const f32x4*>(Qb + (size_t)row * ld + 4 * (c16 ^ ((4 * i + r4) & 15)));
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(ol + (4 * i + r4) * 256 + (c16 << 4)) = t[i];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(ol + rr * 256 + (((8 * h + j) ^ (rr & 15)) << 4));
+      qf[4 * j] = v[0]; qf[4 * j + 1] = v[1]; qf[4 * j + 2] = v[2]; qf[4 * j + 3] = v[3];
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  float m = -INFINITY, l = 0.f;
+  f32x16 o[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+  for (int c0 = 0; c0 < L; c0 += LONGF_KC) {
+    const int rows = min(LONGF_KC, (L - c0 + 31) & ~31);
+    __syncthreads();                                    // every wave is done with the previous chunk
+    for (int r0 = 4 * wave; r0 < rows; r0 += 4 * LONGF_WAVES) {   // 4 rows x 256 B per instruction
+      const int row = min(c0 + r0 + r4, L - 1);
+      __builtin_amdgcn_global_load_lds(GLOBAL_PTR(Kb + (size_t)row * ld + 4 * (c16 ^ ((r0 + r4) & 15))), LDS_PTR(kimg + r0 * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(GLOBAL_PTR(Vb + (size_t)row * ld + 4 * c16), LDS_PTR(vimg + r0 * 256), 16, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (!active) continue;
+    for (int kt = 0; kt < (rows >> 5); ++kt) {
+      const int kbase = c0 + 32 * kt;
+      float kf[32];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(kimg + (32 * kt + rr) * 256 + (((8 * h + j) ^ (rr & 15)) << 4));
+        kf[4 * j] = v[0]; kf[4 * j + 1] = v[1]; kf[4 * j + 2] = v[2]; kf[4 * j + 3] = v[3];
+      }
+      f32x16 st;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) st[e] = 0.f;
+#pragma unroll
+      for (int s2 = 0; s2 < 32; ++s2) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s2], qf[s2], st, 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = kbase + (e & 3) + 8 * (e >> 2) + 4 * h;
+        st[e] = key < L ? st[e] * 0.125f : -INFINITY;            // scores / sqrt(64), as the reference scales them
+      }
+      float tmx = st[0];
+#pragma unroll
+      for (int e = 1; e < 16; ++e) tmx = fmaxf(tmx, st[e]);
+      tmx = fmaxf(tmx, __shfl_xor(tmx, 32, 64));
+      const float mn = fmaxf(m, tmx);
+      float rs = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { st[e] = expf(st[e] - mn); rs += st[e]; }
+      rs += __shfl_xor(rs, 32, 64);
+      const float alpha = kbase == 0 ? 0.f : expf(m - mn);
+      l = l * alpha + rs;
+      if (kbase > 0) {
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) o[dt][e] *= alpha;
+      }
+      m = mn;
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const char* vrow = vimg + (32 * kt + 8 * (t >> 2) + (t & 3) + 4 * h) * 256 + rr * 4;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          const float vv = *reinterpret_cast<const float*>(vrow + 128 * dt);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv, st[t], o[dt], 0, 0, 0);
+        }
+      }
+    }
+  }
+  if (!active) return;
+  // O^T -> ctx rows (or the split operand) through the wave's slab: lane (query rr, half h) owns features 32dt + 8g + 4h .. +3
+  const float inv = 1.0f / l;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c = (32 * dt + 8 * g + 4 * h) >> 2;
+      *reinterpret_cast<f32x4*>(ol + rr * 256 + ((c ^ (rr & 15)) << 4)) =
+          f32x4{o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv};
+    }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = 4 * i + r4;
+    const int q = q0 + row;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(ol + row * 256 + (c16 << 4));
+    if (q < L) {
+      const size_t col = head * 64 + 4 * (c16 ^ (row & 15));
+      if (!a3) *reinterpret_cast<f32x4*>(ctx + (size_t)(tok0 + q) * H + col) = v;
+      else if (a3_dt == DT_F16) store_split4<f16_t>(static_cast<f16_t*>(a3) + (size_t)(tok0 + q) * 3 * H + col, H, v);
+      else store_split4<bf16_t>(static_cast<bf16_t*>(a3) + (size_t)(tok0 + q) * 3 * H + col, H, v);
+    }
+  }
 }
 
 // ---- last layer: one query ([CLS]) per news.  One wave per (news, head); lane (g = lane>>3,
@@ -673,6 +971,65 @@ template <> struct Row8<float> {
   }
 };
 
+// [CLS] of a long row (L > MANNER_HIP_MAX_LEN): the same lane layout and arithmetic, the softmax online over 128-key blocks (16 score
+// registers per lane, as the short body holds): running max m, per-lane partial sum and output rescaled by exp(m_old - m_new).
+template <typename T>
+__device__ __forceinline__ void attn_cls_long(const T* __restrict__ Kb, const T* __restrict__ Vb, const float (&q)[8], int L, size_t ld,
+                                              int g, T* __restrict__ dst) {
+  constexpr int MAXR = MANNER_HIP_MAX_LEN / 8;
+  float m = -INFINITY, sum = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int b0 = 0; b0 < L; b0 += MANNER_HIP_MAX_LEN) {
+    float sc[MAXR];
+    float bm = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < MAXR; ++r) {
+      const int key = b0 + 8 * r + g;
+      float s = -INFINITY;
+      if (b0 + 8 * r < L) {                           // wave-uniform
+        float kr[8];
+        Row8<T>::load(Kb + (size_t)min(key, L - 1) * ld, kr);
+        float d = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d = fmaf(q[e], kr[e], d);
+        d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64);
+        s = key < L ? d * 0.125f : -INFINITY;
+      }
+      sc[r] = s;
+      bm = fmaxf(bm, s);
+    }
+    bm = fmaxf(bm, __shfl_xor(bm, 8, 64)); bm = fmaxf(bm, __shfl_xor(bm, 16, 64)); bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float mn = fmaxf(m, bm);                    // finite: every block holds key b0 < L
+    const float alpha = b0 == 0 ? 0.f : expf(m - mn);
+    sum *= alpha;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] *= alpha;
+    m = mn;
+#pragma unroll
+    for (int r = 0; r < MAXR; ++r) {
+      if (b0 + 8 * r < L) {
+        const int key = b0 + 8 * r + g;
+        const float p = expf(sc[r] - mn);             // 0 for masked keys
+        sum += p;
+        float vr[8];
+        Row8<T>::load(Vb + (size_t)min(key, L - 1) * ld, vr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = fmaf(p, vr[e], o[e]);
+      }
+    }
+  }
+  sum += __shfl_xor(sum, 8, 64); sum += __shfl_xor(sum, 16, 64); sum += __shfl_xor(sum, 32, 64);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    o[e] += __shfl_xor(o[e], 8, 64); o[e] += __shfl_xor(o[e], 16, 64); o[e] += __shfl_xor(o[e], 32, 64);
+  }
+  if (g == 0) {
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] *= inv;
+    Row8<T>::store(dst, o);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void attn_cls_kernel(const T* __restrict__ qcls, const T* __restrict__ kv,
                                                        T* __restrict__ ctx, const int32_t* __restrict__ cu,
@@ -687,6 +1044,10 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const T* __restrict__ qcl
   const T* Vb = Kb + H;
   float q[8];
   Row8<T>::load(qcls + (size_t)n * H + head * 64 + 8 * c, q);
+  if (L > MANNER_HIP_MAX_LEN) {                       // wave-uniform: a long row (inference only)
+    attn_cls_long<T>(Kb, Vb, q, L, ld, g, ctx + (size_t)n * H + head * 64 + 8 * c);
+    return;
+  }
   constexpr int MAXR = MANNER_HIP_MAX_LEN / 8;       // 16 key rows per lane group
   float sc[MAXR];
   float mx = -INFINITY;
@@ -754,14 +1115,56 @@ int attention_cls(DType dt, const void* qcls, const void* kv, void* ctx_cls, con
   return MANNER_HIP_OK;
 }
 
+// rows of MANNER_HIP_MAX_LEN < L <= max_len: the long-row kernels, one workgroup per (news, head, query block), rows of <= 128 tokens
+// returning at once (the short kernels did them)
+static int attention_long(DType dt, const void* qkv, void* ctx, const int32_t* cu, int64_t pairs, int heads, int H, int max_len,
+                          hipStream_t stream, void* split_out, DType split_dt) {
+  if (is_16bit(dt)) {
+    const int n_qb = (max_len + 32 * LONG16_WAVES - 1) / (32 * LONG16_WAVES);
+    const int rows_cap = (max_len + 31) / 32 * 32;
+    const int lds = rows_cap * 256 + LONG16_WAVES * 4096;   // K + V images of the whole row + one output slab per wave
+    static bool lds_raised_dev[MAX_DEVICES] = {};
+    bool& lds_raised = lds_raised_dev[current_device_slot()];
+    if (!lds_raised) {
+      const int cap = MANNER_HIP_MAX_LEN_INFER * 256 + LONG16_WAVES * 4096;   // 160 KiB
+      MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_long16_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+      MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_long16_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+      lds_raised = true;
+    }
+    const dim3 grid((unsigned)(pairs * n_qb)), block(64 * LONG16_WAVES);
+    if (dt == DT_F16)
+      hipLaunchKernelGGL(attn_long16_kernel<f16_t>, grid, block, lds, stream, static_cast<const f16_t*>(qkv), static_cast<f16_t*>(ctx), cu,
+                         pairs, n_qb, heads, H, rows_cap);
+    else
+      hipLaunchKernelGGL(attn_long16_kernel<bf16_t>, grid, block, lds, stream, static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(ctx), cu,
+                         pairs, n_qb, heads, H, rows_cap);
+  } else {
+    const int n_qb = (max_len + 32 * LONGF_WAVES - 1) / (32 * LONGF_WAVES);
+    static bool lds_raised_dev[MAX_DEVICES] = {};
+    bool& lds_raised = lds_raised_dev[current_device_slot()];
+    if (!lds_raised) {
+      MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_long_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LONGF_LDS));
+      lds_raised = true;
+    }
+    hipLaunchKernelGGL(attn_long_f32_kernel, dim3((unsigned)(pairs * n_qb)), dim3(64 * LONGF_WAVES), LONGF_LDS, stream,
+                       static_cast<const float*>(qkv), static_cast<float*>(ctx), cu, pairs, n_qb, heads, H, split_out, (int)split_dt);
+  }
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
 int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, int64_t n_news, int heads, int H,
                      int max_len, hipStream_t stream, void* split_out, DType split_dt) {
   if (H != heads * 64) return fail(MANNER_HIP_E_INVALID, "head_dim must be 64 (H=%d heads=%d)", H, heads);
-  if (max_len < 1 || max_len > MANNER_HIP_MAX_LEN)
-    return fail(MANNER_HIP_E_INVALID, "padded length %d exceeds the %d-token attention tile", max_len, MANNER_HIP_MAX_LEN);
+  if (max_len < 1 || max_len > MANNER_HIP_MAX_LEN_INFER)
+    return fail(MANNER_HIP_E_INVALID, "padded length %d outside [1, %d]", max_len, MANNER_HIP_MAX_LEN_INFER);
   const int64_t pairs = n_news * heads;
+  // the short kernels' images hold at most four key tiles: a call that may carry longer rows sizes them for 128 tokens (its long rows
+  // are skipped there and done by attention_long below)
+  const bool long_rows = max_len > MANNER_HIP_MAX_LEN;
+  const int short_len = long_rows ? MANNER_HIP_MAX_LEN : max_len;
   if (is_16bit(dt)) {
-    const int nkt = (max_len + 31) / 32;
+    const int nkt = (short_len + 31) / 32;
     const int lds_per_wave = nkt * 32 * 128 + 4096;   // V image + the 32-query output slab
     static bool lds_raised_dev[MAX_DEVICES] = {};     // 4 waves x 20 KiB exceeds the 64 KiB default of dynamic LDS
     bool& lds_raised = lds_raised_dev[current_device_slot()];   // the attribute is per device
@@ -782,7 +1185,7 @@ int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, in
       hipLaunchKernelGGL(attn_f32_kernel, dim3((unsigned)pairs), dim3(128), 0, stream, static_cast<const float*>(qkv),
                          static_cast<float*>(ctx), cu, heads, H);
     } else {
-      const int nkt = (max_len + 31) / 32;
+      const int nkt = (short_len + 31) / 32;
       const int lds_per_wave = nkt * 32 * 256 + 8192;   // f32 V image (or its two 16-bit halves) + the 32-row slab
       static bool lds_raised_dev[MAX_DEVICES] = {};
       bool& lds_raised = lds_raised_dev[current_device_slot()];
@@ -806,15 +1209,15 @@ int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, in
         else if (nkt == 3) MANNER_ATTN_X3(3);
         else MANNER_ATTN_X3(4);
 #undef MANNER_ATTN_X3
-        MANNER_LAUNCH_CHECK();
-        return MANNER_HIP_OK;
+      } else {
+        hipLaunchKernelGGL(attn_f32_mfma_kernel, dim3((unsigned)((pairs + 1) / 2)), dim3(128), 2 * lds_per_wave, stream,
+                           static_cast<const float*>(qkv), static_cast<float*>(ctx), cu, pairs, heads, H, lds_per_wave, split_out,
+                           (int)split_dt);
       }
-      hipLaunchKernelGGL(attn_f32_mfma_kernel, dim3((unsigned)((pairs + 1) / 2)), dim3(128), 2 * lds_per_wave, stream,
-                         static_cast<const float*>(qkv), static_cast<float*>(ctx), cu, pairs, heads, H, lds_per_wave, split_out,
-                         (int)split_dt);
     }
   }
   MANNER_LAUNCH_CHECK();
+  if (long_rows) return attention_long(dt, qkv, ctx, cu, pairs, heads, H, max_len, stream, split_out, split_dt);
   return MANNER_HIP_OK;
 }
 

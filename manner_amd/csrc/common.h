@@ -123,10 +123,11 @@ int pool_fused(const float* x, const float* W, const float* bias, const float* q
 // m_bound: rows the chunk's buffers hold; expect_tokens >= 0: what the caller's host_lengths promised.  A mask that
 // yields more tokens than m_bound is truncated there (cu[n] clamped to m_bound - 1 for a news START, cu[n_news] to m_bound:
 // every row index cu[n] + t, t < len, and every [CLS] row cu[n] stays below m_bound) and, like any disagreement with
-// expect_tokens, raises MANNER_HIP_STATUS_LENGTHS.
+// expect_tokens, raises MANNER_HIP_STATUS_LENGTHS.  max_len: the caller's per-row token limit (MANNER_HIP_MAX_LEN_INFER for the
+// inference driver, MANNER_HIP_MAX_LEN for training); a longer row raises MANNER_HIP_STATUS_MASK.
 int lengths_and_offsets(const int64_t* mask, int64_t n_news, int64_t padded_len, int32_t* lens,
                         int32_t* cu /*[n_news+1]*/, int32_t* m_total /*[2]: tokens, news*/, int64_t m_bound,
-                        int64_t expect_tokens, int32_t* status, hipStream_t stream);
+                        int64_t expect_tokens, int32_t* status, hipStream_t stream, int max_len);
 int embed_layernorm(DType out, const int64_t* ids, int64_t n_news, int64_t padded_len, const int32_t* cu,
                     const float* word, const float* pos, const float* type0, const float* gamma,
                     const float* beta, int H, float eps, int pos_offset, int vocab, int max_pos,

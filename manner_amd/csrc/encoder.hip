@@ -205,7 +205,8 @@ int encode_chunk(manner_hip_encoder* e, const int64_t* ids, const int64_t* mask,
   int rc;
   {
     ProfScope ps(e, s, MANNER_HIP_PROF_LENGTHS);
-    if ((rc = lengths_and_offsets(mask, n_news, lp, ws.lens, ws.cu, ws.m_total, m_bound, expect_tokens, e->status, s))) return rc;
+    if ((rc = lengths_and_offsets(mask, n_news, lp, ws.lens, ws.cu, ws.m_total, m_bound, expect_tokens, e->status, s,
+                                 MANNER_HIP_MAX_LEN_INFER))) return rc;
   }
   const int pos_offset = c.arch == MANNER_HIP_ARCH_ROBERTA ? c.pad_id + 1 : 0;
 #define PROF_STEP(cls, call) { ProfScope ps(e, s, cls); if ((rc = (call))) return rc; }
@@ -566,7 +567,8 @@ static int encode_impl(manner_hip_encoder_t enc, const int64_t* ids, const int64
   if (n_news == 0) return MANNER_HIP_OK;
   if (!ids || !mask || !out || !workspace || n_news < 0) return fail(MANNER_HIP_E_INVALID, "encode_cls: null pointer");
   if (precision < 0 || precision > 4 || !(enc->precisions & (1u << precision))) return fail(MANNER_HIP_E_INVALID, "encode_cls: precision %d was not requested at encoder_create", precision);
-  if (padded_len < 1 || padded_len > MANNER_HIP_MAX_LEN) return fail(MANNER_HIP_E_INVALID, "encode_cls: padded_len %lld outside [1, %d]", (long long)padded_len, MANNER_HIP_MAX_LEN);
+  // rows of up to MANNER_HIP_MAX_LEN_INFER tokens: those beyond the short-row tile (MANNER_HIP_MAX_LEN) take the long-row attention
+  if (padded_len < 1 || padded_len > MANNER_HIP_MAX_LEN_INFER) return fail(MANNER_HIP_E_INVALID, "encode_cls: padded_len %lld outside [1, %d]", (long long)padded_len, MANNER_HIP_MAX_LEN_INFER);
   if ((uintptr_t)workspace % 256) return fail(MANNER_HIP_E_INVALID, "encode_cls: workspace must be 256-byte aligned");
   const int H = enc->cfg.hidden;
   // largest (news, tokens) chunk capacity the workspace admits: tokens scale the big buffers.
@@ -702,7 +704,7 @@ int manner_hip_encoder_status(manner_hip_encoder_t enc, manner_hip_stream_t stre
   MANNER_HIP_TRY(hipMemcpyAsync(&flag, enc->status, sizeof(flag), hipMemcpyDeviceToHost, s));
   MANNER_HIP_TRY(hipMemsetAsync(enc->status, 0, sizeof(flag), s));
   MANNER_HIP_TRY(hipStreamSynchronize(s));
-  if (flag & MANNER_HIP_STATUS_MASK) return fail(MANNER_HIP_E_INPUT, "attention_mask is not a right-padded 0/1 prefix mask with 1..%d real tokens per news", MANNER_HIP_MAX_LEN);
+  if (flag & MANNER_HIP_STATUS_MASK) return fail(MANNER_HIP_E_INPUT, "attention_mask is not a right-padded 0/1 prefix mask with 1..%d real tokens per news", MANNER_HIP_MAX_LEN_INFER);
   if (flag & MANNER_HIP_STATUS_TOKEN) return fail(MANNER_HIP_E_INPUT, "input_ids or position index out of range of the embedding tables");
   if (flag & MANNER_HIP_STATUS_LENGTHS) return fail(MANNER_HIP_E_INPUT, "host_lengths disagree with the row sums of attention_mask (tokens beyond the chunk bound were dropped)");
   if (flag) return fail(MANNER_HIP_E_INPUT, "device status word 0x%x", flag);

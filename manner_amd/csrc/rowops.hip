@@ -16,10 +16,10 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// ---- lengths: one wave per news; validates that mask is a 0/1 prefix with 1 <= len <= MAX_LEN
+// ---- lengths: one wave per news; validates that mask is a 0/1 prefix with 1 <= len <= max_len (the caller's per-row limit)
 __global__ __launch_bounds__(256) void lengths_kernel(const int64_t* __restrict__ mask, int64_t n_news,
                                                       int64_t lp, int32_t* __restrict__ lens,
-                                                      int32_t* __restrict__ status) {
+                                                      int32_t* __restrict__ status, int max_len) {
   const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (n >= n_news) return;
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void lengths_kernel(const int64_t* __restrict_
     last_one = max(last_one, __shfl_xor(last_one, o, 64));
   }
   if (last_one + 1 != cnt) bad = 1;                      // a hole: not a prefix mask
-  if (cnt < 1 || cnt > MANNER_HIP_MAX_LEN) bad = 1;
+  if (cnt < 1 || cnt > max_len) bad = 1;
   if (lane == 0) {
     lens[n] = bad ? 1 : cnt;                             // keep downstream indexing in bounds
     if (bad) atomicOr(status, 1);
@@ -390,9 +390,10 @@ __global__ __launch_bounds__(256) void cvt_16_kernel(const float* __restrict__ s
 }  // namespace
 
 int lengths_and_offsets(const int64_t* mask, int64_t n_news, int64_t padded_len, int32_t* lens, int32_t* cu,
-                        int32_t* m_total, int64_t m_bound, int64_t expect_tokens, int32_t* status, hipStream_t stream) {
+                        int32_t* m_total, int64_t m_bound, int64_t expect_tokens, int32_t* status, hipStream_t stream,
+                        int max_len) {
   hipLaunchKernelGGL(lengths_kernel, dim3((unsigned)((n_news + 3) / 4)), dim3(256), 0, stream, mask, n_news,
-                     padded_len, lens, status);
+                     padded_len, lens, status, max_len);
   MANNER_LAUNCH_CHECK();
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, lens, n_news, cu, m_total,
                      (int)min(m_bound, (int64_t)0x7fffffff), (int)expect_tokens, status);

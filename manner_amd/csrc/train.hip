@@ -1675,7 +1675,7 @@ int manner_hip_encode_full(const manner_hip_encoder_config* cfg, const float* co
   const size_t wide = (size_t)(cfg->intermediate > 3 * H ? cfg->intermediate : 3 * H);
   MANNER_HIP_TRY(hipMemsetAsync(t.wk.zero, 0, wide * sizeof(float), s));
   // real lengths (validated like every other entry point) = key counts; rows = every position
-  if ((rc = lengths_and_offsets(mask, n_news, padded_len, f.lens, f.cu_real, f.m_real, Mb, -1, status, s))) return rc;
+  if ((rc = lengths_and_offsets(mask, n_news, padded_len, f.lens, f.cu_real, f.m_real, Mb, -1, status, s, MANNER_HIP_MAX_LEN))) return rc;
   hipLaunchKernelGGL(full_offsets_kernel, dim3((unsigned)((n_news + 256) / 256)), dim3(256), 0, s, f.cu_full, f.m_total, n_news, (int)padded_len);
   MANNER_LAUNCH_CHECK();
   const bool roberta = cfg->arch == MANNER_HIP_ARCH_ROBERTA;
@@ -1726,10 +1726,10 @@ static int train_forward_impl(const manner_hip_encoder_config* cfg, const float*
   if (full) {
     if (start_layer != 0 || m_bound != round_up(n_news * padded_len, 256)) return fail(MANNER_HIP_E_INVALID, "train_full_forward: m_bound must be round_up(n_news * padded_len, 256)");
     // real lengths (validated as everywhere) = key counts; the packed offsets they imply are scratch (wk.dsum / wk.dims)
-    if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, reinterpret_cast<int32_t*>(t.wk.dsum), t.wk.dims + 8, m_bound, -1, status, s))) return rc;
+    if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, reinterpret_cast<int32_t*>(t.wk.dsum), t.wk.dims + 8, m_bound, -1, status, s, MANNER_HIP_MAX_LEN))) return rc;
     hipLaunchKernelGGL(full_offsets_kernel, dim3((unsigned)((n_news + 256) / 256)), dim3(256), 0, s, sv.cu, sv.m_total, n_news, (int)padded_len);
     MANNER_LAUNCH_CHECK();
-  } else if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, sv.cu, sv.m_total, m_bound, -1, status, s))) {
+  } else if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, sv.cu, sv.m_total, m_bound, -1, status, s, MANNER_HIP_MAX_LEN))) {
     return rc;
   }
   float* x0 = sv.l[start_layer].x_in;
