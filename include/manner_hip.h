@@ -40,8 +40,8 @@ enum {
  * (the encoder handle's own, or the caller-owned int32 `status` argument of the scoring entry points, which may be
  * NULL) and continue on a safe substitute.  The reference raises a Python exception in each of these cases. */
 enum {
-  MANNER_HIP_STATUS_MASK = 1,     /* attention_mask is not a right-padded 0/1 prefix with 1..MAX_LEN_INFER tokens (inference) or
-                                     1..MAX_LEN tokens (training) */
+  MANNER_HIP_STATUS_MASK = 1,     /* attention_mask is not a right-padded 0/1 prefix with 1..MAX_LEN_INFER tokens (inference),
+                                     1..MAX_LEN_TRAIN tokens (train_forward / _backward) or 1..MAX_LEN tokens ("full rows") */
   MANNER_HIP_STATUS_TOKEN = 2,    /* input id / position outside the embedding tables (IndexError in the reference) */
   MANNER_HIP_STATUS_FUSED = 4,    /* reserved (bounded-wait overflow of a fused kernel) */
   MANNER_HIP_STATUS_INDEX = 8,    /* news / entity index outside the table (IndexError in the reference) */
@@ -163,11 +163,14 @@ int manner_hip_encoder_status(manner_hip_encoder_t enc, manner_hip_stream_t stre
  * both on `stream`; the caller reads *host_flag once an event recorded after this call has completed.  This is how
  * the module mirror surfaces bad inputs of call k at call k+1 without a host synchronisation per forward. */
 int manner_hip_encoder_status_async(manner_hip_encoder_t enc, int32_t* host_flag /*pinned host*/, manner_hip_stream_t stream);
-/* Per-row token limits.  MANNER_HIP_MAX_LEN: the training path (manner_hip_encode_full, the train_* entry points) and the
- * short-row attention tile (at most four 32-key tiles per wave).  MANNER_HIP_MAX_LEN_INFER: the inference entry points
- * manner_hip_encode_cls / manner_hip_encode_hidden, whose rows of 129..512 tokens run the long-row attention kernels. */
+/* Per-row token limits.  MANNER_HIP_MAX_LEN: the "full rows" entry points (manner_hip_encode_full, manner_hip_train_full_*) and
+ * the short-row attention tile (at most four 32-key tiles per wave).  MANNER_HIP_MAX_LEN_INFER: the inference entry points
+ * manner_hip_encode_cls / manner_hip_encode_hidden, whose rows of 129..512 tokens run the long-row attention kernels.
+ * MANNER_HIP_MAX_LEN_TRAIN: manner_hip_train_forward / _backward, whose rows of 129..512 tokens run the long-row training
+ * attention kernels (the rows of <= 128 tokens keep the short-row kernels and their bits). */
 #define MANNER_HIP_MAX_LEN 128
 #define MANNER_HIP_MAX_LEN_INFER 512
+#define MANNER_HIP_MAX_LEN_TRAIN 512
 
 /* ABI v8 — sampled fingerprint of a set of tensors, for hosts that cache copies of caller-owned parameters (the module mirror's
  * inference handle packs the PLM weights once; torch's version counters do not see a write through `p.data`).  out[i] = a 32-bit
@@ -404,7 +407,10 @@ int manner_hip_eval_loss(const float* scores, const float* labels, const int64_t
  *
  *   weights : HOST array of n_weights device pointers (f32, the order of manner_hip_encoder_create) — the live master
  *             parameters, read at every call (nothing is cached between optimiser steps);
- *   ids / mask / n_news / padded_len : as manner_hip_encode_cls (padded_len <= MANNER_HIP_MAX_LEN);
+ *   ids / mask / n_news / padded_len : as manner_hip_encode_cls, padded_len <= MANNER_HIP_MAX_LEN_TRAIN (512); every row must
+ *             also fit the model's position table (MANNER_HIP_STATUS_TOKEN otherwise).  Rows of more than MANNER_HIP_MAX_LEN (128)
+ *             tokens run the long-row attention kernels (one workgroup per news, head and block of queries or keys);
+ *             `saved` and `workspace` stay per token (nothing of size tokens^2 is stored);
  *   m_bound : rows every activation buffer holds: a multiple of 256, >= the number of real tokens (n_news * padded_len
  *             rounded up always works; a device-side check raises MANNER_HIP_STATUS_LENGTHS otherwise);
  *   precision : MANNER_HIP_PREC_F32 (f32 MFMA GEMMs) or _F16 / _BF16 (GEMM operands rounded to 16 bits, f32 accumulation,
@@ -416,7 +422,9 @@ int manner_hip_eval_loss(const float* scores, const float* labels, const int64_t
  *   seed    : dropout masks are a pure function of (seed, site, element index); the backward call must repeat the
  *             forward call's seed and probabilities.  manner_hip_dropout_mask returns the keep-bits of one site
  *             (site 0: embeddings over [m, H]; 1: [CLS] output over [n_news, H]; 8*(layer+1)+0: attention
- *             probabilities over [(m*heads + head)*256 + key]; +1: attention output; +2: FFN output, over [m, H]);
+ *             probabilities over [(m*heads + head)*256 + key] for a query row m of a news of <= 128 tokens, and — a stream
+ *             of its own — site (8*(layer+1)) | 0x80000000 over [((m*heads + head) << 9) + key] for a news of 129..512 tokens;
+ *             +1: attention output; +2: FFN output, over [m, H]);
  *   saved   : manner_hip_train_saved_bytes(cfg, n_news, m_bound, start_layer) bytes that carry the activations from the
  *             forward to the backward call;  workspace: manner_hip_train_workspace_bytes(cfg, m_bound) bytes of scratch;
  *   cls_out : f32 [n_news, H].
@@ -475,7 +483,7 @@ int manner_hip_dropout_mask(uint64_t seed, uint32_t site, float p, int64_t n, ui
  * nrms_plm_module.py:119-135): every position of the padded batch is a row (m = n_news * padded_len), the real tokens
  * of a news are its attention keys, padded positions embed the pad token (RoBERTa: at position pad_id) and still
  * produce outputs, no layer is pruned to the [CLS] rows.  hidden / grad_hidden: f32 [n_news * padded_len, H] (row
- * n * padded_len + t).  saved: manner_hip_train_saved_bytes(cfg, n_news, M, 0), workspace:
+ * n * padded_len + t); padded_len <= MANNER_HIP_MAX_LEN (128).  saved: manner_hip_train_saved_bytes(cfg, n_news, M, 0), workspace:
  * manner_hip_train_workspace_bytes(cfg, M), M = n_news * padded_len rounded up to 256.  Dropout sites and the grads
  * table as in manner_hip_train_forward / _backward (there is no [CLS] dropout here: the caller owns what follows). */
 int manner_hip_train_full_forward(const manner_hip_encoder_config* cfg, const float* const* weights /*host*/, int32_t n_weights,

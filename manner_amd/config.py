@@ -71,6 +71,12 @@ PRESETS = {
     "tiny-roberta": EncoderConfig(arch=ARCH_ROBERTA, hidden=128, layers=2, heads=2,
                                   intermediate=512, vocab=2048, max_pos=130, type_vocab=1,
                                   ln_eps=1e-5, pad_id=1),
+    # the tiny shapes with a 512-token position table (BERT 512, RoBERTa 514): long-row training goldens
+    "tiny-bert-512": EncoderConfig(hidden=128, layers=2, heads=2, intermediate=512, vocab=2048,
+                                   max_pos=512),
+    "tiny-roberta-514": EncoderConfig(arch=ARCH_ROBERTA, hidden=128, layers=2, heads=2,
+                                      intermediate=512, vocab=2048, max_pos=514, type_vocab=1,
+                                      ln_eps=1e-5, pad_id=1),
 }
 
 

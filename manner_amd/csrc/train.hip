@@ -18,6 +18,7 @@
 // supplies cached hidden states of a frozen prefix).
 #include <math.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <mutex>
 #include <unordered_map>
 
@@ -508,12 +509,15 @@ __global__ __launch_bounds__(AT) void attn_train_fwd_kernel(const float* __restr
                                                             int H, Drop drop, const int32_t* __restrict__ klen, Out16 o16) {
   constexpr int KC = AttnGeom<HPB>::KC, HS = AttnGeom<HPB>::HS, RPH = AT / (2 * HPB);
   __shared__ __attribute__((aligned(16))) float ks[HPB * HS], vs[HPB * HS];
-  const int hs = threadIdx.x / (2 * RPH), i = (threadIdx.x - hs * 2 * RPH) >> 1, half = threadIdx.x & 1;
+  const int hs = threadIdx.x / (2 * RPH), i = (int)blockIdx.z * RPH + ((threadIdx.x - hs * 2 * RPH) >> 1), half = threadIdx.x & 1;
   const int h0 = blockIdx.x * HPB, h = h0 + hs;
   const int64_t n = blockIdx.y;
   const int base = cu[n], S = cu[n + 1] - base;
+  if (blockIdx.z > 0 && (int)blockIdx.z * RPH >= S) return;   // workgroup-uniform: a row block past this news
   const bool active = i < S;
   const int SK = klen ? min(klen[n], S) : S;
+  const Drop dr = attn_drop_for(drop, S);
+  const int dsh = attn_drop_shift(S);
   const size_t ld = (size_t)3 * H;
   const float* rows = qkv + (size_t)base * ld;
   float q[AH], o[AH];
@@ -542,7 +546,7 @@ __global__ __launch_bounds__(AT) void attn_train_fwd_kernel(const float* __restr
       }
       const float p = expf(s - mx);
       l += p;
-      const float pd = drop.apply(p, ((uint64_t)(base + i) * heads + h) * 256 + (uint64_t)(j0 + j));
+      const float pd = dr.apply(p, (((uint64_t)(base + i) * heads + h) << dsh) + (uint64_t)(j0 + j));
 #pragma unroll
       for (int d = 0; d < AH; ++d) o[d] = fmaf(pd, vh[j * RS + d], o[d]);
     }
@@ -567,12 +571,15 @@ __global__ __launch_bounds__(AT) void attn_train_bwd_q_kernel(const float* __res
                                                               const int32_t* __restrict__ klen) {
   constexpr int KC = AttnGeom<HPB>::KC, HS = AttnGeom<HPB>::HS, RPH = AT / (2 * HPB);
   __shared__ __attribute__((aligned(16))) float ks[HPB * HS], vs[HPB * HS];
-  const int hs = threadIdx.x / (2 * RPH), i = (threadIdx.x - hs * 2 * RPH) >> 1, half = threadIdx.x & 1;
+  const int hs = threadIdx.x / (2 * RPH), i = (int)blockIdx.z * RPH + ((threadIdx.x - hs * 2 * RPH) >> 1), half = threadIdx.x & 1;
   const int h0 = blockIdx.x * HPB, h = h0 + hs;
   const int64_t n = blockIdx.y;
   const int base = cu[n], SQ_ = cu[n + 1] - base;
+  if (blockIdx.z > 0 && (int)blockIdx.z * RPH >= SQ_) return;  // workgroup-uniform: a row block past this news
   const int S = klen ? min(klen[n], SQ_) : SQ_;             // keys; every row of the news is a query
   const bool active = i < SQ_;
+  const Drop dr = attn_drop_for(drop, SQ_);
+  const int dsh = attn_drop_shift(SQ_);
   const size_t ld = (size_t)3 * H;
   const float* rows = qkv + (size_t)base * ld;
   float q[AH], go[AH], dq[AH];
@@ -602,7 +609,7 @@ __global__ __launch_bounds__(AT) void attn_train_bwd_q_kernel(const float* __res
       s = pair_sum(s);
       gv = pair_sum(gv);
       const float p = expf(s - st.x) * inv;
-      const float dp = drop.apply(gv, ((uint64_t)(base + i) * heads + h) * 256 + (uint64_t)(j0 + j));
+      const float dp = dr.apply(gv, (((uint64_t)(base + i) * heads + h) << dsh) + (uint64_t)(j0 + j));
       const float ds = p * (dp - D) * 0.125f;
 #pragma unroll
       for (int d = 0; d < AH; ++d) dq[d] = fmaf(ds, kh[j * RS + d], dq[d]);
@@ -626,10 +633,13 @@ __global__ __launch_bounds__(AT) void attn_train_bwd_kv_kernel(const float* __re
   constexpr int KC = AttnGeom<HPB>::KC, HS = AttnGeom<HPB>::HS, RPH = AT / (2 * HPB);
   __shared__ __attribute__((aligned(16))) float qs[HPB * HS], gs[HPB * HS];
   __shared__ float sm[HPB][KC], sl[HPB][KC], sd[HPB][KC];
-  const int hs = threadIdx.x / (2 * RPH), j = (threadIdx.x - hs * 2 * RPH) >> 1, half = threadIdx.x & 1;
+  const int hs = threadIdx.x / (2 * RPH), j = (int)blockIdx.z * RPH + ((threadIdx.x - hs * 2 * RPH) >> 1), half = threadIdx.x & 1;
   const int h0 = blockIdx.x * HPB, h = h0 + hs;
   const int64_t n = blockIdx.y;
   const int base = cu[n], S = cu[n + 1] - base;             // queries: every row; a row past klen is no key: its d k = d v = 0
+  if (blockIdx.z > 0 && (int)blockIdx.z * RPH >= S) return;   // workgroup-uniform: a row block past this news
+  const Drop dr = attn_drop_for(drop, S);
+  const int dsh = attn_drop_shift(S);
   const bool active = j < S;
   const bool is_key = !klen || j < klen[n];
   const size_t ld = (size_t)3 * H;
@@ -664,9 +674,9 @@ __global__ __launch_bounds__(AT) void attn_train_bwd_kv_kernel(const float* __re
       s = pair_sum(s);
       gv = pair_sum(gv);
       const float p = expf(s - sm[hs][i]) * sl[hs][i];
-      const uint64_t idx = ((uint64_t)(base + i0 + i) * heads + h) * 256 + (uint64_t)j;
-      const float dp = drop.apply(gv, idx);
-      const float pd = drop.apply(p, idx);
+      const uint64_t idx = (((uint64_t)(base + i0 + i) * heads + h) << dsh) + (uint64_t)j;
+      const float dp = dr.apply(gv, idx);
+      const float pd = dr.apply(p, idx);
       const float ds = p * (dp - sd[hs][i]);         // qs already carries the 1/8
 #pragma unroll
       for (int d = 0; d < AH; ++d) { dk[d] = fmaf(ds, qh[i * RS + d], dk[d]); dv[d] = fmaf(pd, gh[i * RS + d], dv[d]); }
@@ -684,7 +694,9 @@ __global__ __launch_bounds__(AT) void attn_train_bwd_kv_kernel(const float* __re
   for (int d = 0; d < AH; d += 8) { put16x8(o16, ck + d, dk + d); put16x8(o16, cv + d, dv + d); }
 }
 
-// launch geometry from the padded length (<= MANNER_HIP_MAX_LEN = 128): two lanes per row; rows per head = 16 / 32 / 64 / 128
+// launch geometry from the padded length capped at MANNER_HIP_MAX_LEN = 128: two lanes per row; rows per head = 16 / 32 / 64 / 128.
+// Longer rows (training, up to MANNER_HIP_MAX_LEN_TRAIN) take the 128-row geometry with a grid dimension z of row blocks (rows
+// 128 z .. 128 z + 127 of each news as queries, resp. keys; the other side streamed whole); a padded length <= 128 launches z = 1.
 #define MANNER_ATTN_DISPATCH(LP, HEADS, CALL)                   \
   do {                                                          \
     if ((LP) <= 16 && (HEADS) % 2 == 0) { CALL(64, 2); }        \
@@ -1004,14 +1016,15 @@ void plan_work(Bump& b, Work& w, const manner_hip_encoder_config& c, int64_t Mb)
   w.dims = b.take<int32_t>(16);
 }
 
-int check_cfg(const manner_hip_encoder_config* c, int64_t N, int64_t Lp, int64_t Mb, int32_t precision, int start) {
+int check_cfg(const manner_hip_encoder_config* c, int64_t N, int64_t Lp, int64_t Mb, int32_t precision, int start,
+              int max_len = MANNER_HIP_MAX_LEN_TRAIN) {
   if (!c) return fail(MANNER_HIP_E_INVALID, "train: null config");
   if (c->hidden % 128 || c->intermediate % 128 || c->hidden / c->heads != AD || c->hidden % c->heads || c->hidden > 64 * LN_MAX ||
       c->layers <= 0 || c->layers > 64)
     return fail(MANNER_HIP_E_INVALID, "train: unsupported architecture H=%d I=%d heads=%d layers=%d", c->hidden, c->intermediate,
                 c->heads, c->layers);
-  if (N <= 0 || Lp <= 0 || Lp > MANNER_HIP_MAX_LEN)
-    return fail(MANNER_HIP_E_INVALID, "train: n_news=%lld padded_len=%lld (padded_len <= %d, as the inference engine)", (long long)N, (long long)Lp, MANNER_HIP_MAX_LEN);
+  if (N <= 0 || Lp <= 0 || Lp > max_len)
+    return fail(MANNER_HIP_E_INVALID, "train: n_news=%lld padded_len=%lld (padded_len <= %d)", (long long)N, (long long)Lp, max_len);
   if (Mb <= 0 || Mb % 256 || Mb > 0x7fffff00ll / (3 * (int64_t)c->hidden)) return fail(MANNER_HIP_E_INVALID, "train: m_bound=%lld must be a positive multiple of 256 within int range", (long long)Mb);
   if (Mb < round_up(N, 256)) return fail(MANNER_HIP_E_INVALID, "train: m_bound=%lld holds fewer rows than there are news (%lld): every news has a token", (long long)Mb, (long long)N);
   if (precision != MANNER_HIP_PREC_F32 && precision != MANNER_HIP_PREC_BF16 && precision != MANNER_HIP_PREC_F16)
@@ -1500,10 +1513,11 @@ int layer_forward(Ctx& t, int l, LayerSaved& L, const float* x_in, float* x_out,
   } else {
     if ((rc = linear_fwd(t, x_in, t.wk.wcat, t.wk.bcat, L.qkv, 3 * H, H, mixed && x_in_has_16 ? t.wk.h16a : nullptr))) return rc;
     const Drop da = da_m;
+    const unsigned zb = (unsigned)((t.Lp + MANNER_HIP_MAX_LEN - 1) / MANNER_HIP_MAX_LEN);
 #define MANNER_ATTN_FWD(AT_, HPB_)                                                                                             \
-  hipLaunchKernelGGL((attn_train_fwd_kernel<AT_, HPB_>), dim3((unsigned)(cfg->heads / HPB_), (unsigned)t.N), dim3(AT_), 0, s, L.qkv, \
+  hipLaunchKernelGGL((attn_train_fwd_kernel<AT_, HPB_>), dim3((unsigned)(cfg->heads / HPB_), (unsigned)t.N, zb), dim3(AT_), 0, s, L.qkv, \
                      L.ctx, L.ml, cu, cfg->heads, H, da, klen, t.o16(t.wk.h16b))
-    MANNER_ATTN_DISPATCH(t.Lp, cfg->heads, MANNER_ATTN_FWD);
+    MANNER_ATTN_DISPATCH(std::min<int64_t>(t.Lp, MANNER_HIP_MAX_LEN), cfg->heads, MANNER_ATTN_FWD);
 #undef MANNER_ATTN_FWD
     MANNER_LAUNCH_CHECK();
   }
@@ -1658,7 +1672,7 @@ int manner_hip_encode_full(const manner_hip_encoder_config* cfg, const float* co
   int rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t Mb = round_up(n_news * padded_len, 256);
-  if ((rc = check_cfg(cfg, n_news, padded_len, Mb, precision, 0))) return rc;
+  if ((rc = check_cfg(cfg, n_news, padded_len, Mb, precision, 0, MANNER_HIP_MAX_LEN))) return rc;
   if (!weights || n_weights != MANNER_HIP_W_EMB_COUNT + cfg->layers * MANNER_HIP_WL_COUNT) return fail(MANNER_HIP_E_INVALID, "encode_full: weight table size");
   for (int i = 0; i < n_weights; ++i)
     if (!weights[i]) return fail(MANNER_HIP_E_INVALID, "encode_full: weight %d is NULL", i);
@@ -1726,10 +1740,10 @@ static int train_forward_impl(const manner_hip_encoder_config* cfg, const float*
   if (full) {
     if (start_layer != 0 || m_bound != round_up(n_news * padded_len, 256)) return fail(MANNER_HIP_E_INVALID, "train_full_forward: m_bound must be round_up(n_news * padded_len, 256)");
     // real lengths (validated as everywhere) = key counts; the packed offsets they imply are scratch (wk.dsum / wk.dims)
-    if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, reinterpret_cast<int32_t*>(t.wk.dsum), t.wk.dims + 8, m_bound, -1, status, s, MANNER_HIP_MAX_LEN))) return rc;
+    if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, reinterpret_cast<int32_t*>(t.wk.dsum), t.wk.dims + 8, m_bound, -1, status, s, MANNER_HIP_MAX_LEN_TRAIN))) return rc;
     hipLaunchKernelGGL(full_offsets_kernel, dim3((unsigned)((n_news + 256) / 256)), dim3(256), 0, s, sv.cu, sv.m_total, n_news, (int)padded_len);
     MANNER_LAUNCH_CHECK();
-  } else if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, sv.cu, sv.m_total, m_bound, -1, status, s, MANNER_HIP_MAX_LEN))) {
+  } else if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, sv.cu, sv.m_total, m_bound, -1, status, s, MANNER_HIP_MAX_LEN_TRAIN))) {
     return rc;
   }
   float* x0 = sv.l[start_layer].x_in;
@@ -2005,11 +2019,12 @@ static int train_backward_impl(const manner_hip_encoder_config* cfg, const float
     } else {
 #define MANNER_ATTN_BWD(AT_, HPB_)                                                                                              \
   do {                                                                                                                            \
-    const dim3 ag((unsigned)(cfg->heads / HPB_), (unsigned)n_news);                                                               \
+    const dim3 ag((unsigned)(cfg->heads / HPB_), (unsigned)n_news, zb);                                                           \
     hipLaunchKernelGGL((attn_train_bwd_q_kernel<AT_, HPB_>), ag, dim3(AT_), 0, s, L.qkv, wk.dx, L.ctx, L.ml, wk.dqkv, wk.dsum, sv.cu, cfg->heads, H, da, t.o16(b_dqkv), full ? sv.lens : nullptr);  \
     hipLaunchKernelGGL((attn_train_bwd_kv_kernel<AT_, HPB_>), ag, dim3(AT_), 0, s, L.qkv, wk.dx, L.ml, wk.dsum, wk.dqkv, sv.cu, cfg->heads, H, da, t.o16(b_dqkv), full ? sv.lens : nullptr); \
   } while (0)
-    MANNER_ATTN_DISPATCH(padded_len, cfg->heads, MANNER_ATTN_BWD);
+    const unsigned zb = (unsigned)((padded_len + MANNER_HIP_MAX_LEN - 1) / MANNER_HIP_MAX_LEN);
+    MANNER_ATTN_DISPATCH(std::min<int64_t>(padded_len, MANNER_HIP_MAX_LEN), cfg->heads, MANNER_ATTN_BWD);
 #undef MANNER_ATTN_BWD
     MANNER_LAUNCH_CHECK();
     }
@@ -2108,6 +2123,8 @@ int manner_hip_train_full_forward(const manner_hip_encoder_config* cfg, const fl
                                   float p_hidden, float p_attn, uint64_t seed, float* hidden, void* saved, size_t saved_bytes,
                                   void* workspace, size_t workspace_bytes, int32_t* status, manner_hip_stream_t stream) {
   if (n_news <= 0 || padded_len <= 0) return fail(MANNER_HIP_E_INVALID, "train_full_forward: empty batch");
+  if (padded_len > MANNER_HIP_MAX_LEN)
+    return fail(MANNER_HIP_E_INVALID, "train_full_forward: padded_len=%lld (padded_len <= %d)", (long long)padded_len, MANNER_HIP_MAX_LEN);
   return train_forward_impl(cfg, weights, n_weights, ids, mask, n_news, padded_len, round_up(n_news * padded_len, 256), precision, 0, nullptr,
                             p_hidden, p_attn, 0.f, seed, hidden, saved, saved_bytes, workspace, workspace_bytes, status, stream, true);
 }
@@ -2117,6 +2134,8 @@ int manner_hip_train_full_backward(const manner_hip_encoder_config* cfg, const f
                                    float p_attn, uint64_t seed, const float* grad_hidden, void* saved, size_t saved_bytes,
                                    float* const* grads, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream) {
   if (n_news <= 0 || padded_len <= 0) return fail(MANNER_HIP_E_INVALID, "train_full_backward: empty batch");
+  if (padded_len > MANNER_HIP_MAX_LEN)
+    return fail(MANNER_HIP_E_INVALID, "train_full_backward: padded_len=%lld (padded_len <= %d)", (long long)padded_len, MANNER_HIP_MAX_LEN);
   return train_backward_impl(cfg, weights, n_weights, ids, n_news, padded_len, round_up(n_news * padded_len, 256), precision, 0, p_hidden,
                              p_attn, 0.f, seed, grad_hidden, saved, saved_bytes, grads, nullptr, workspace, workspace_bytes, stream, true);
 }

@@ -16,7 +16,11 @@
 // backward-kv  (lane = key)    S = Q K^T, dP = dO V^T, dV^T += dO^T (M P), dK^T += Q^T dS         — no atomics anywhere
 // with D_i = dctx_i . ctx_i (= sum_j dP_ij P_ij; ctx carries the same dropout) from a small pre-pass that also writes the
 // 16-bit copy of dctx.  Dropout bits are regenerated from (seed, site, (row * heads + head) * 256 + key) in all three.
+// News of 129 .. 512 tokens (training's MANNER_HIP_MAX_LEN_TRAIN) run the *_long_kernel passes below (one workgroup per news, head
+// and block of rows; the short kernels return at once for them), with a dropout stream of their own (attn_drop_for).
 #include <math.h>
+
+#include <algorithm>
 
 #include "train_common.h"
 
@@ -214,7 +218,7 @@ __global__ __launch_bounds__(256) void attn_train_mfma_fwd_kernel(const TE* __re
   const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
   const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
-  if (L <= 0) return;
+  if (L <= 0 || L > MANNER_HIP_MAX_LEN) return;             // wave-uniform: a long row (the *_long_kernel of this pass)
   char* vl = vlds + wave * lds_per_wave;
   // NKTMAX = key tiles of the batch's padded length: a title-length batch compiles to the one-tile body only (few registers,
   // 8 KiB of LDS per wave -> many waves per CU); the host guarantees L <= 32 NKTMAX
@@ -337,7 +341,7 @@ __global__ __launch_bounds__(256) void attn_train_mfma_bwd_q_kernel(const TE* __
   const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
   const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
-  if (L <= 0) return;
+  if (L <= 0 || L > MANNER_HIP_MAX_LEN) return;             // wave-uniform: a long row (the *_long_kernel of this pass)
   char* vl = vlds + wave * lds_per_wave;
   // NKTMAX = key tiles of the batch's padded length: a title-length batch compiles to the one-tile body only (few registers,
   // 8 KiB of LDS per wave -> many waves per CU); the host guarantees L <= 32 NKTMAX
@@ -436,7 +440,7 @@ __global__ __launch_bounds__(256) void attn_train_mfma_bwd_kv_kernel(const TE* _
   const int n = (int)(pair / heads), head = (int)(pair - (int64_t)n * heads);
   const int tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   const int L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
-  if (L <= 0) return;
+  if (L <= 0 || L > MANNER_HIP_MAX_LEN) return;             // wave-uniform: a long row (the *_long_kernel of this pass)
   char* vl = vlds + wave * lds_per_wave;
   // NKTMAX = key tiles of the batch's padded length: a title-length batch compiles to the one-tile body only (few registers,
   // 8 KiB of LDS per wave -> many waves per CU); the host guarantees L <= 32 NKTMAX
@@ -444,6 +448,283 @@ __global__ __launch_bounds__(256) void attn_train_mfma_bwd_kv_kernel(const TE* _
   else if (NKTMAX == 2 || L <= 64) { if constexpr (NKTMAX >= 2) bwd_kv_wave<TE, 2>(qkv, dctx16, ml, dsum, dqkv, dqkv16, tok0, L, H, heads, head, vl, drop); }
   else if (NKTMAX == 3 || L <= 96) { if constexpr (NKTMAX >= 3) bwd_kv_wave<TE, 3>(qkv, dctx16, ml, dsum, dqkv, dqkv16, tok0, L, H, heads, head, vl, drop); }
   else { if constexpr (NKTMAX >= 4) bwd_kv_wave<TE, 4>(qkv, dctx16, ml, dsum, dqkv, dqkv16, tok0, L, H, heads, head, vl, drop); }
+}
+
+// ------------------------------------------------------------------------------------------------ long rows
+// Rows of MANNER_HIP_MAX_LEN < L <= MANNER_HIP_MAX_LEN_TRAIN tokens: one workgroup of W waves per (news, head, block of 32 W rows),
+// each wave owning 32 rows of the lane side — queries (forward, backward-q) or keys (backward-kv) — with the arithmetic of the wave
+// functions above.  The other side's two matrices of the WHOLE row are staged once per workgroup by LDS-DMA before one barrier, as
+// attention.hip's attn_long16_kernel does (2 x 64 KiB at 512 tokens).  Both images are chunk-swizzled like the slab (16-byte chunk
+// c of row r at c ^ ((r >> 1) & 7)), so that one image serves the fragment reads (img_frags) and the transposed reads
+// (tr_frag_swz: ds_read_b64_tr_b16 takes a per-lane address, which goes through the same swizzle).  Rows >= L of the last tile
+// replicate row L - 1 (finite; masked or weighted by 0).  LDS at 512 tokens:
+//   forward     K and V images + eight 4 KiB slabs (8 waves, 256 queries)                                     160 KiB
+//   backward-q  K and V images + eight slabs (8 waves, 256 queries)                                           160 KiB
+//   backward-kv Q and d ctx images + {-max C, 1 / sum, D} per query (12 B a row) + four slabs (4 waves, 128 keys)  150 KiB
+// Dropout: the long-row stream (attn_drop_for / attn_drop_shift); the kernels return at once for a row of <= 128 tokens.
+constexpr int LONG_FWD_WAVES = 8, LONG_Q_WAVES = 8, LONG_KV_WAVES = 4;
+constexpr int LONG_LDS_FWD = MANNER_HIP_MAX_LEN_TRAIN * 256 + LONG_FWD_WAVES * 4096;
+constexpr int LONG_LDS_Q = MANNER_HIP_MAX_LEN_TRAIN * 256 + LONG_Q_WAVES * 4096;
+constexpr int LONG_LDS_KV = MANNER_HIP_MAX_LEN_TRAIN * (256 + 12) + LONG_KV_WAVES * 4096;
+static_assert(LONG_LDS_FWD <= 160 * 1024 && LONG_LDS_Q <= 160 * 1024 && LONG_LDS_KV <= 160 * 1024, "long-row LDS beyond the CU's 160 KiB");
+
+// rows 0 .. nrows - 1 (nrows % 8 == 0, clamped to L - 1) of a 64-feature 16-bit matrix into a swizzled image: the workgroup's W waves
+// take every W-th piece of 8 rows x 128 B, each lane fetching the source chunk that belongs at its lane-linear destination
+template <typename TE>
+__device__ __forceinline__ void dma_image_swz(const TE* __restrict__ base, size_t ld, int L, int nrows, char* img, int wave, int W) {
+  const int lane = threadIdx.x & 63, r8 = lane >> 3, c8 = lane & 7;
+  for (int r0 = 8 * wave; r0 < nrows; r0 += 8 * W) {
+    const int row = min(r0 + r8, L - 1);
+    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(base + (size_t)row * ld + 8 * (c8 ^ (((r0 + r8) >> 1) & 7))), LDS_PTR(img + r0 * 128), 16, 0, 0);
+  }
+}
+// operand fragments of tile `tile` of a swizzled image: lane (rr, h) holds row 32 tile + rr, features 16 ks + 8 h .. + 7 (tile_to_frags)
+template <typename TE>
+__device__ __forceinline__ void img_frags(const char* img, int tile, typename E16<TE>::v8 (&f)[4]) {
+  typedef typename E16<TE>::v8 e16x8;
+  const int lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) f[ks] = *reinterpret_cast<const e16x8*>(img + (32 * tile + rr) * 128 + (((2 * ks + h) ^ ((rr >> 1) & 7)) << 4));
+}
+// tr_frag of a swizzled image: lane 4 q + p of 16-lane group (b, h) reads row 32 tile + 16 s2 + 4 h + q (and + 8), bytes 64 dt + 32 b + 8 p
+template <typename TE>
+__device__ __forceinline__ typename E16<TE>::v8 tr_frag_swz(const char* img, int tile, int s2, int dt) {
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const int lane = threadIdx.x & 63, gi = lane & 15, q = gi >> 2, p = gi & 3, b = (lane >> 4) & 1, h = lane >> 5;
+  const int row = 32 * tile + 16 * s2 + 4 * h + q, ch = 4 * dt + 2 * b + (p >> 1);
+  const char* lo_a = img + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4) + 8 * (p & 1);
+  const char* hi_a = img + (row + 8) * 128 + ((ch ^ (((row + 8) >> 1) & 7)) << 4) + 8 * (p & 1);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lo_a));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(hi_a));
+  const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(typename E16<TE>::v8, both);
+}
+// the (news, head, block) of a long-row workgroup: false (workgroup-uniform) for a short row or a block past the row's end
+__device__ __forceinline__ bool long_block(const int32_t* __restrict__ cu, int64_t n_pairs, int n_blk, int heads, int rows_per_blk,
+                                           int& tok0, int& L, int& head, int& blk) {
+  const int64_t pair = (int64_t)blockIdx.x / n_blk;
+  blk = (int)((int64_t)blockIdx.x - pair * n_blk);
+  if (pair >= n_pairs) return false;
+  const int n = (int)(pair / heads);
+  head = (int)(pair - (int64_t)n * heads);
+  tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
+  L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
+  return L > MANNER_HIP_MAX_LEN && rows_per_blk * blk < L;
+}
+
+template <typename TE>
+__global__ __launch_bounds__(64 * LONG_FWD_WAVES, 1) void attn_train_mfma_fwd_long_kernel(const TE* __restrict__ qkv, float* __restrict__ ctx,
+                                                                                         TE* __restrict__ ctx16, float2* __restrict__ ml,
+                                                                                         const int32_t* __restrict__ cu, int64_t n_pairs,
+                                                                                         int n_blk, int heads, int H, int rows_cap, Drop drop) {
+  typedef typename E16<TE>::v8 e16x8;
+  constexpr int W = LONG_FWD_WAVES;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  int tok0, L, head, blk;
+  if (!long_block(cu, n_pairs, n_blk, heads, 32 * W, tok0, L, head, blk)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
+  char* kimg = lds;
+  char* vimg = lds + (size_t)rows_cap * 128;
+  char* ol = lds + (size_t)rows_cap * 256 + wave * 4096;
+  const size_t ld = 3 * (size_t)H;
+  const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
+  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;
+  const int q0 = 32 * W * blk + 32 * wave;
+  e16x8 qf[4];
+  fetch_frags<TE>(Qb, ld, q0, L, ol, qf);
+  dma_image_swz<TE>(Qb + H, ld, L, nrows, kimg, wave, W);
+  dma_image_swz<TE>(Qb + 2 * H, ld, L, nrows, vimg, wave, W);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's share of the images (LDS-DMA is not tracked by the compiler)
+  __syncthreads();                                        // ... and every other wave's
+  if (q0 >= L) return;                                    // wave-uniform: no query of this wave is real (no barrier follows)
+  const Drop dr = attn_drop_for(drop, L);
+  const int q = q0 + rr;
+  const uint64_t didx0 = ((uint64_t)(tok0 + q) * heads + head) << attn_drop_shift(L);
+  float m = -INFINITY, l = 0.f;
+  f32x16 o[2] = {zero16(), zero16()};
+  for (int kt = 0; kt < nkt; ++kt) {
+    e16x8 kf[4];
+    img_frags<TE>(kimg, kt, kf);
+    f32x16 st = zero16();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) st = E16<TE>::mfma32(kf[ks], qf[ks], st);
+    if (32 * kt + 32 > L) {                               // wave-uniform: the last tile holds keys >= L
+#pragma unroll
+      for (int e = 0; e < 16; ++e) st[e] = 32 * kt + acc_row(e, h) < L ? st[e] : -INFINITY;
+    }
+    float tmx = st[0];
+#pragma unroll
+    for (int e = 1; e < 16; ++e) tmx = fmaxf(tmx, st[e]);
+    tmx = fmaxf(tmx, __shfl_xor(tmx, 32, 64));
+    const float mn = fmaxf(m, tmx);                       // finite: tile 0 always holds key 0 < L
+    const float nmc = -mn * kC;
+    float rs = 0.f;
+    e16x8 pf[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float p = __builtin_amdgcn_exp2f(fmaf(st[e], kC, nmc));   // exp((s - max) / 8); 0 for masked keys
+      rs += p;
+      pf[e >> 3][e & 7] = (TE)dr.apply(p, didx0 + (uint64_t)(32 * kt + acc_row(e, h)));
+    }
+    rs += __shfl_xor(rs, 32, 64);
+    if (kt == 0) {
+      l = rs;
+    } else {
+      const float alpha = __builtin_amdgcn_exp2f((m - mn) * kC);
+      l = l * alpha + rs;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[dt][e] *= alpha;
+    }
+    m = mn;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) o[dt] = E16<TE>::mfma32(tr_frag_swz<TE>(vimg, kt, s2, dt), pf[s2], o[dt]);
+  }
+  store_rows<TE>(ol, o, 1.0f / l, q0, L, ctx ? ctx + (size_t)tok0 * H + head * 64 : nullptr, (size_t)H,
+                 ctx16 ? ctx16 + (size_t)tok0 * H + head * 64 : nullptr, (size_t)H);
+  if (h == 0 && q < L) ml[(size_t)(tok0 + q) * heads + head] = float2{m, l};
+}
+
+template <typename TE>
+__global__ __launch_bounds__(64 * LONG_Q_WAVES, 1) void attn_train_mfma_bwd_q_long_kernel(const TE* __restrict__ qkv, const TE* __restrict__ dctx16,
+                                                                                         const float2* __restrict__ ml, const float* __restrict__ dsum,
+                                                                                         float* __restrict__ dqkv, TE* __restrict__ dqkv16,
+                                                                                         const int32_t* __restrict__ cu, int64_t n_pairs,
+                                                                                         int n_blk, int heads, int H, int rows_cap, Drop drop) {
+  typedef typename E16<TE>::v8 e16x8;
+  constexpr int W = LONG_Q_WAVES;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  int tok0, L, head, blk;
+  if (!long_block(cu, n_pairs, n_blk, heads, 32 * W, tok0, L, head, blk)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
+  char* kimg = lds;
+  char* vimg = lds + (size_t)rows_cap * 128;
+  char* ol = lds + (size_t)rows_cap * 256 + wave * 4096;
+  const size_t ld = 3 * (size_t)H;
+  const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
+  const TE* Gb = dctx16 + (size_t)tok0 * H + head * 64;
+  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;
+  const int q0 = 32 * W * blk + 32 * wave;
+  e16x8 qf[4], gf[4];
+  fetch_frags<TE>(Qb, ld, q0, L, ol, qf);
+  fetch_frags<TE>(Gb, (size_t)H, q0, L, ol, gf);
+  const int q = min(q0 + rr, L - 1);
+  const float2 st2 = ml[(size_t)(tok0 + q) * heads + head];
+  const float nmc = -st2.x * kC, invl = 1.0f / st2.y;
+  const float D = dsum[(size_t)(tok0 + q) * heads + head];
+  dma_image_swz<TE>(Qb + H, ld, L, nrows, kimg, wave, W);
+  dma_image_swz<TE>(Qb + 2 * H, ld, L, nrows, vimg, wave, W);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (q0 >= L) return;
+  const Drop dr = attn_drop_for(drop, L);
+  const uint64_t didx0 = ((uint64_t)(tok0 + q0 + rr) * heads + head) << attn_drop_shift(L);
+  f32x16 dq[2] = {zero16(), zero16()};
+  for (int kt = 0; kt < nkt; ++kt) {
+    e16x8 kf[4], vf[4];
+    img_frags<TE>(kimg, kt, kf);
+    img_frags<TE>(vimg, kt, vf);
+    f32x16 st = zero16(), dp = zero16();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      st = E16<TE>::mfma32(kf[ks], qf[ks], st);
+      dp = E16<TE>::mfma32(vf[ks], gf[ks], dp);
+    }
+    e16x8 dsf[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int key = 32 * kt + acc_row(e, h);
+      const float p = key < L ? __builtin_amdgcn_exp2f(fmaf(st[e], kC, nmc)) * invl : 0.f;
+      const float g = dr.apply(dp[e], didx0 + (uint64_t)key);
+      dsf[e >> 3][e & 7] = (TE)(p * (g - D) * 0.125f);
+    }
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) dq[dt] = E16<TE>::mfma32(tr_frag_swz<TE>(kimg, kt, s2, dt), dsf[s2], dq[dt]);
+  }
+  store_rows<TE>(ol, dq, 1.0f, q0, L, dqkv ? dqkv + (size_t)tok0 * ld + head * 64 : nullptr, ld,
+                 dqkv16 ? dqkv16 + (size_t)tok0 * ld + head * 64 : nullptr, ld);
+}
+
+template <typename TE>
+__global__ __launch_bounds__(64 * LONG_KV_WAVES, 1) void attn_train_mfma_bwd_kv_long_kernel(const TE* __restrict__ qkv, const TE* __restrict__ dctx16,
+                                                                                           const float2* __restrict__ ml, const float* __restrict__ dsum,
+                                                                                           float* __restrict__ dqkv, TE* __restrict__ dqkv16,
+                                                                                           const int32_t* __restrict__ cu, int64_t n_pairs,
+                                                                                           int n_blk, int heads, int H, int rows_cap, Drop drop) {
+  typedef typename E16<TE>::v8 e16x8;
+  constexpr int W = LONG_KV_WAVES;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  int tok0, L, head, blk;
+  if (!long_block(cu, n_pairs, n_blk, heads, 32 * W, tok0, L, head, blk)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
+  char* qimg = lds;                                       // Q image, d ctx image, row statistics, slabs
+  char* gimg = lds + (size_t)rows_cap * 128;
+  float* sm = reinterpret_cast<float*>(lds + (size_t)rows_cap * 256);   // [rows_cap] -max * C, [rows_cap] 1 / sum, [rows_cap] D
+  float* sl = sm + rows_cap;
+  float* sd = sl + rows_cap;
+  char* ol = lds + (size_t)rows_cap * (256 + 12) + wave * 4096;
+  const size_t ld = 3 * (size_t)H;
+  const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
+  const TE* Gb = dctx16 + (size_t)tok0 * H + head * 64;
+  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;
+  const int k0 = 32 * W * blk + 32 * wave;
+  e16x8 kfb[4], vfb[4];
+  fetch_frags<TE>(Qb + H, ld, k0, L, ol, kfb);
+  fetch_frags<TE>(Qb + 2 * H, ld, k0, L, ol, vfb);
+  dma_image_swz<TE>(Qb, ld, L, nrows, qimg, wave, W);
+  dma_image_swz<TE>(Gb, (size_t)H, L, nrows, gimg, wave, W);
+  for (int r = threadIdx.x; r < nrows; r += 64 * W) {
+    const int row = min(r, L - 1);
+    const float2 st2 = ml[(size_t)(tok0 + row) * heads + head];
+    sm[r] = -st2.x * kC;
+    sl[r] = 1.0f / st2.y;
+    sd[r] = dsum[(size_t)(tok0 + row) * heads + head];
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (k0 >= L) return;
+  const Drop dr = attn_drop_for(drop, L);
+  const int dsh = attn_drop_shift(L);
+  const int key = k0 + rr;
+  f32x16 dk[2] = {zero16(), zero16()}, dv[2] = {zero16(), zero16()};
+  for (int qt = 0; qt < nkt; ++qt) {
+    e16x8 qf[4], gf[4];
+    img_frags<TE>(qimg, qt, qf);
+    img_frags<TE>(gimg, qt, gf);
+    f32x16 s = zero16(), dp = zero16();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      s = E16<TE>::mfma32(qf[ks], kfb[ks], s);            // [query][key]: lane = key rr, 16 queries per lane
+      dp = E16<TE>::mfma32(gf[ks], vfb[ks], dp);
+    }
+    e16x8 pdf[2], dsf[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int qi = 32 * qt + acc_row(e, h);
+      const float p = qi < L ? __builtin_amdgcn_exp2f(fmaf(s[e], kC, sm[qi])) * sl[qi] : 0.f;
+      const bool keep = dr.thr == 0 || drop_bits(dr.seed, dr.site, (((uint64_t)(tok0 + qi) * heads + head) << dsh) + (uint64_t)key) >= dr.thr;
+      const float pd = keep ? p * dr.scale : 0.f;
+      const float g = keep ? dp[e] * dr.scale : 0.f;
+      pdf[e >> 3][e & 7] = (TE)pd;
+      dsf[e >> 3][e & 7] = (TE)(p * (g - sd[qi]) * 0.125f);
+    }
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        dv[dt] = E16<TE>::mfma32(tr_frag_swz<TE>(gimg, qt, s2, dt), pdf[s2], dv[dt]);
+        dk[dt] = E16<TE>::mfma32(tr_frag_swz<TE>(qimg, qt, s2, dt), dsf[s2], dk[dt]);
+      }
+  }
+  store_rows<TE>(ol, dk, 1.0f, k0, L, dqkv ? dqkv + (size_t)tok0 * ld + H + head * 64 : nullptr, ld,
+                 dqkv16 ? dqkv16 + (size_t)tok0 * ld + H + head * 64 : nullptr, ld);
+  store_rows<TE>(ol, dv, 1.0f, k0, L, dqkv ? dqkv + (size_t)tok0 * ld + 2 * H + head * 64 : nullptr, ld,
+                 dqkv16 ? dqkv16 + (size_t)tok0 * ld + 2 * H + head * 64 : nullptr, ld);
 }
 
 constexpr int MAX_LDS_FWD = 4 * (4 * 4096 + 4096);                 // 4 waves x (V image of 4 tiles + slab)
@@ -456,13 +737,21 @@ int raise_lds() {
   MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_kv_kernel<TE, NKTMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_KV));
   return MANNER_HIP_OK;
 }
+template <typename TE>
+int raise_lds_long() {
+  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_fwd_long_kernel<TE>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_FWD));
+  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_q_long_kernel<TE>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_Q));
+  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_kv_long_kernel<TE>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_KV));
+  return MANNER_HIP_OK;
+}
 int ensure_lds() {
   static bool raised[MAX_DEVICES] = {};
   bool& r = raised[current_device_slot()];
   if (!r) {
     int rc;
     if ((rc = raise_lds<f16_t, 1>()) || (rc = raise_lds<f16_t, 2>()) || (rc = raise_lds<f16_t, 3>()) || (rc = raise_lds<f16_t, 4>()) ||
-        (rc = raise_lds<bf16_t, 1>()) || (rc = raise_lds<bf16_t, 2>()) || (rc = raise_lds<bf16_t, 3>()) || (rc = raise_lds<bf16_t, 4>()))
+        (rc = raise_lds<bf16_t, 1>()) || (rc = raise_lds<bf16_t, 2>()) || (rc = raise_lds<bf16_t, 3>()) || (rc = raise_lds<bf16_t, 4>()) ||
+        (rc = raise_lds_long<f16_t>()) || (rc = raise_lds_long<bf16_t>()))
       return rc;
     r = true;
   }
@@ -472,8 +761,25 @@ int ensure_lds() {
 int check_shape(DType dt, int heads, int H, int max_len) {
   if (!is_16bit(dt)) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: 16-bit element types only");
   if (H != heads * 64 || H % 8) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: head_dim must be 64 (H=%d heads=%d)", H, heads);
-  if (max_len < 1 || max_len > MANNER_HIP_MAX_LEN) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: padded length %d outside [1, %d]", max_len, MANNER_HIP_MAX_LEN);
+  if (max_len < 1 || max_len > MANNER_HIP_MAX_LEN_TRAIN)
+    return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: padded length %d outside [1, %d]", max_len, MANNER_HIP_MAX_LEN_TRAIN);
   return MANNER_HIP_OK;
+}
+
+// the short-row kernels' tile count: rows of <= 128 tokens (a longer padded length launches the four-tile body, whose
+// kernels return at once for its long rows)
+int short_tiles(int max_len) { return (std::min(max_len, (int)MANNER_HIP_MAX_LEN) + 31) / 32; }
+// the long-row launch of a pass of W waves: grid (news x heads x blocks of 32 W rows), LDS sized by the padded length
+struct LongGrid {
+  unsigned grid;
+  int n_blk, rows_cap;
+};
+LongGrid long_grid(int64_t pairs, int max_len, int W) {
+  LongGrid g;
+  g.n_blk = (max_len + 32 * W - 1) / (32 * W);
+  g.rows_cap = (max_len + 31) & ~31;
+  g.grid = (unsigned)(pairs * g.n_blk);
+  return g;
 }
 
 }  // namespace
@@ -483,7 +789,7 @@ int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16
   int rc;
   if ((rc = check_shape(dt, heads, H, max_len)) || (rc = ensure_lds())) return rc;
   const int64_t pairs = n_news * heads;
-  const int nkt = (max_len + 31) / 32;
+  const int nkt = short_tiles(max_len);
   const int lds_per_wave = nkt * 4096 + 4096;
   const dim3 g((unsigned)((pairs + 3) / 4)), b(256);
 #define MANNER_ATTN_FWD_LAUNCH(TE_, N_)                                                                                                   \
@@ -495,6 +801,17 @@ int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16
   else MANNER_ATTN_BY_NKT(MANNER_ATTN_FWD_LAUNCH, bf16_t);
 #undef MANNER_ATTN_FWD_LAUNCH
   MANNER_LAUNCH_CHECK();
+  if (max_len > MANNER_HIP_MAX_LEN) {                         // rows of 129 .. max_len tokens (the short kernels skipped them)
+    const LongGrid lg = long_grid(pairs, max_len, LONG_FWD_WAVES);
+    const size_t lds = (size_t)lg.rows_cap * 256 + LONG_FWD_WAVES * 4096;
+#define MANNER_ATTN_FWD_LONG(TE_)                                                                                                          \
+  hipLaunchKernelGGL(attn_train_mfma_fwd_long_kernel<TE_>, dim3(lg.grid), dim3(64 * LONG_FWD_WAVES), lds, stream, static_cast<const TE_*>(qkv16), \
+                     ctx, static_cast<TE_*>(ctx16), ml, cu, pairs, lg.n_blk, heads, H, lg.rows_cap, drop)
+    if (dt == DT_F16) MANNER_ATTN_FWD_LONG(f16_t);
+    else MANNER_ATTN_FWD_LONG(bf16_t);
+#undef MANNER_ATTN_FWD_LONG
+    MANNER_LAUNCH_CHECK();
+  }
   return MANNER_HIP_OK;
 }
 
@@ -506,7 +823,7 @@ int attn_train_mfma_backward(DType dt, const void* qkv16, const void* dctx, bool
   if (!dqkv && !dqkv16) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma_backward: no output");
   if (dctx_is16) dctx16 = const_cast<void*>(dctx);          // d ctx arrived in the 16-bit type: it IS the operand of the two kernels
   const int64_t pairs = n_news * heads;
-  const int nkt = (max_len + 31) / 32;
+  const int nkt = short_tiles(max_len);
   const int lds_q = nkt * 4096 + 4096, lds_kv = 2 * nkt * 4096 + 4096 + 2048;
   const dim3 g((unsigned)((pairs + 3) / 4)), b(256), gp((unsigned)((m_bound + 3) / 4));
 #define MANNER_ATTN_BWD_LAUNCH(TE_, N_)                                                                                                      \
@@ -532,6 +849,23 @@ int attn_train_mfma_backward(DType dt, const void* qkv16, const void* dctx, bool
   else MANNER_ATTN_BY_NKT(MANNER_ATTN_BWD_LAUNCH, bf16_t);
 #undef MANNER_ATTN_BWD_LAUNCH
   MANNER_LAUNCH_CHECK();
+  if (max_len > MANNER_HIP_MAX_LEN) {                         // rows of 129 .. max_len tokens, after the pre-pass above
+    const LongGrid lq = long_grid(pairs, max_len, LONG_Q_WAVES), lkv = long_grid(pairs, max_len, LONG_KV_WAVES);
+    const size_t lds_lq = (size_t)lq.rows_cap * 256 + LONG_Q_WAVES * 4096, lds_lkv = (size_t)lkv.rows_cap * (256 + 12) + LONG_KV_WAVES * 4096;
+#define MANNER_ATTN_BWD_LONG(TE_)                                                                                                             \
+  do {                                                                                                                                        \
+    hipLaunchKernelGGL(attn_train_mfma_bwd_q_long_kernel<TE_>, dim3(lq.grid), dim3(64 * LONG_Q_WAVES), lds_lq, stream,                         \
+                       static_cast<const TE_*>(qkv16), static_cast<const TE_*>(dctx16), ml, dsum, dqkv, static_cast<TE_*>(dqkv16), cu, pairs,  \
+                       lq.n_blk, heads, H, lq.rows_cap, drop);                                                                                 \
+    hipLaunchKernelGGL(attn_train_mfma_bwd_kv_long_kernel<TE_>, dim3(lkv.grid), dim3(64 * LONG_KV_WAVES), lds_lkv, stream,                     \
+                       static_cast<const TE_*>(qkv16), static_cast<const TE_*>(dctx16), ml, dsum, dqkv, static_cast<TE_*>(dqkv16), cu, pairs,  \
+                       lkv.n_blk, heads, H, lkv.rows_cap, drop);                                                                               \
+  } while (0)
+    if (dt == DT_F16) MANNER_ATTN_BWD_LONG(f16_t);
+    else MANNER_ATTN_BWD_LONG(bf16_t);
+#undef MANNER_ATTN_BWD_LONG
+    MANNER_LAUNCH_CHECK();
+  }
   return MANNER_HIP_OK;
 }
 

@@ -21,6 +21,15 @@ struct Drop {
     return (thr == 0 || drop_bits(seed, site, idx) >= thr) ? v * scale : 0.f;
   }
 };
+// attention-probability dropout, element (query row m, head, key) of a news of L tokens: index ((m * heads + head) << shift) + key.
+// A news of <= MANNER_HIP_MAX_LEN tokens keeps shift 8 under the layer's site; a longer one (keys up to 511: shift 8 would reach the
+// next head's elements) draws from a stream of its own, site | 0x80000000 with shift 9.
+__host__ __device__ __forceinline__ Drop attn_drop_for(const Drop& d, int L) {
+  Drop r = d;
+  if (L > MANNER_HIP_MAX_LEN) r.site |= 0x80000000u;
+  return r;
+}
+__host__ __device__ __forceinline__ int attn_drop_shift(int L) { return L > MANNER_HIP_MAX_LEN ? 9 : 8; }
 static inline Drop make_drop(uint64_t seed, uint32_t site, float p) {
   Drop d;
   d.seed = seed;
@@ -59,14 +68,15 @@ int gemm_tn_gelu_dual16(DType in, const void* X, const void* W, const float* bia
 int gemm_tn_gelu_grad16(DType in, const void* X, const void* W, const float* zero_bias, const void* pre16, void* Y16, int64_t m_bound, int N,
                         int K, const int* m_total, hipStream_t stream);
 
-// Training attention on the matrix pipe (train_attn.hip; 16-bit modes): S <= 128 keys per news, head_dim 64, one wave per
-// (news, head).  qkv16 [m, 3H] = [Q | K | V] of the 16-bit type `dt`.
+// Training attention on the matrix pipe (train_attn.hip; 16-bit modes): head_dim 64, max_len <= MANNER_HIP_MAX_LEN_TRAIN.  A news of
+// <= 128 tokens runs one wave per (news, head); a longer one one workgroup per (news, head, block of queries or keys), K / V (or
+// Q / d ctx) of the whole news in LDS.  qkv16 [m, 3H] = [Q | K | V] of the 16-bit type `dt`.
 //   forward : ctx [m, H] f32 (may be NULL: round 5, 16-bit saved activations) and / or its 16-bit form ctx16 (may be NULL) =
 //             dropout(softmax(q k^T / 8)) v;  ml[m, heads] = {row max of the RAW scores q.k, sum of exp((s - max) / 8)} so that the
 //             backward rebuilds P without a reduction pass.
 //   backward: dsum[m, heads] = dctx . ctx per head first — dctx / ctx f32 or (`*_is16`) of the type `dt`; an f32 dctx is also copied
 //             to dctx16 (scratch [m_bound, H] of `dt`), a 16-bit one is used where it lies — then d qkv [m, 3H] as f32 rows (dqkv,
-//             may be NULL) and / or 16-bit rows (dqkv16, may be NULL).  Dropout bits: element ((row * heads + head) * 256 + key).
+//             may be NULL) and / or 16-bit rows (dqkv16, may be NULL).  Dropout bits: attn_drop_for / attn_drop_shift.
 int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16, float2* ml, const int32_t* cu, int64_t n_news,
                             int heads, int H, int max_len, Drop drop, hipStream_t stream);
 int attn_train_mfma_backward(DType dt, const void* qkv16, const void* dctx, bool dctx_is16, const void* ctx, bool ctx_is16, const float2* ml,

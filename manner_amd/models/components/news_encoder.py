@@ -400,7 +400,12 @@ class MannerTextEncoder(nn.Module):
                 extra = dict(prefix_hidden=ph, start_layer=start)
         return train.encode_train(plm.cfg, params, ids, mask, precision=tp, p_hidden=on * plm.hidden_dropout_prob,
                                   p_attn=on * plm.attention_probs_dropout_prob, p_out=on * self.dropout.p, seed=seed, prefix_engine=engine,
-                                  **extra)
+                                  max_len=self.train_max_length, **extra)
+
+    #: Opt-in: the longest padded batch train() accepts.  128 (the default) keeps the short-row limit; up to 512 trains on news of
+    #: 129..512 tokens (a higher data.tokenizer_max_length), whose attention runs the long-row kernels.  Saved activations grow per
+    #: token (about 31 KB per token and layer at bert-base in the 16-bit modes), so batches of long news must hold fewer news.
+    train_max_length: int = int(os.environ.get("MANNER_HIP_TRAIN_MAX_LEN", "128"))
 
     #: Opt-in: rows of a `hip.PrefixCache` — the hidden states after the frozen layers, kept per news across steps and epochs when the
     #: embeddings and a prefix of layers are frozen.  One row is prefix_cache_len x hidden f32 (96 x 768: 295 KB).

@@ -216,8 +216,13 @@ def first_trainable_layer(cfg: EncoderConfig, params: Dict[str, Tensor]) -> int:
 def encode_train(cfg: EncoderConfig, params: Dict[str, Tensor], ids: Tensor, mask: Tensor, *, precision: str = "f16",
                  p_hidden: float = 0.1, p_attn: float = 0.1, p_out: float = 0.2, seed: int = 0,
                  prefix_engine: Optional[hip.HipEncoder] = None, prefix_hidden: Optional[Tensor] = None,
-                 start_layer: Optional[int] = None, token_bound: Optional[int] = None) -> Tensor:
+                 start_layer: Optional[int] = None, token_bound: Optional[int] = None, max_len: int = _lib.MAX_LEN) -> Tensor:
     """[N, Lp] ids / mask -> [N, H] dropout([CLS]) with autograd into ``params`` (HF-named parameter dict).
+
+    ``max_len``: the longest padded batch this call accepts (``Lp > max_len`` raises ``RuntimeError``).  The default is the
+    128-token limit of the short-row kernels; up to ``_lib.MAX_LEN_TRAIN`` (512) opts in to news of 129..512 tokens, which run the
+    long-row attention kernels (``saved`` grows per token, so such batches hold fewer news).  Every row must also fit the model's
+    position table.
 
     ``start_layer`` / ``prefix_hidden``: explicit cached prefix; by default the prefix is used automatically when no
     tensor below the first trainable layer requires grad and a ``prefix_engine`` (inference HipEncoder over the same
@@ -227,9 +232,15 @@ def encode_train(cfg: EncoderConfig, params: Dict[str, Tensor], ids: Tensor, mas
     at ``hip.check_status`` (blocking)."""
     if precision not in _TRAIN_PRECISIONS:
         raise ValueError(f"training precision {precision!r}: one of {_TRAIN_PRECISIONS}")
+    if not 1 <= int(max_len) <= _lib.MAX_LEN_TRAIN:
+        raise ValueError(f"max_len={max_len}: training takes padded batches of 1..{_lib.MAX_LEN_TRAIN} tokens")
     ids, mask = hip._dev(ids, torch.int64, "input_ids").contiguous(), hip._dev(mask, torch.int64, "attention_mask").contiguous()
     if ids.dim() != 2 or ids.shape != mask.shape:
         raise ValueError(f"input_ids {tuple(ids.shape)} / attention_mask {tuple(mask.shape)} must be equal 2-D")
+    if ids.shape[1] > int(max_len):
+        raise RuntimeError(f"train: padded_len={ids.shape[1]} beyond max_len={int(max_len)} (padded_len <= {int(max_len)}); news of up "
+                           f"to {_lib.MAX_LEN_TRAIN} tokens train with max_len={_lib.MAX_LEN_TRAIN} "
+                           f"(MannerTextEncoder.train_max_length, MANNER_HIP_TRAIN_MAX_LEN)")
     canon = canonical_weights(cfg, params)
     table = [canon[name] for name in hip.weight_table_order(cfg)]
     for name, t in zip(hip.weight_table_order(cfg), table):
