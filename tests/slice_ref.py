@@ -1,0 +1,183 @@
+"""Float64 reference of the encoder and per-slice error maps for the 16-bit attention tests (test_attention_slices_host.py,
+test_gpu_attention_slices.py).  A helper module, not a conftest.
+
+``reference`` restates the oracle's encoder (manner_oracle.encode_tokens / encode_cls_train, whose embedding function it calls)
+in float64, on the operands the 16-bit kernels consume: every weight matrix and embedding table rounded to the mode's 16-bit type
+(biases and LayerNorm parameters stay f32, as the kernels read them), then widened.  Optionally it rounds at the kernels'
+storage points as well (``store``; the inference path's points of tools/precision_sim.py):
+
+  "qkv"    Q | K | V after the fused projection (the 16-bit qkv buffer the attention kernels read)
+  "probs"  the probabilities fed to the PV product (after dropout and its 1 / (1 - p) scale)
+  "ctx"    the attention output (the 16-bit ctx the out-projection GEMM reads)
+  "inter"  the GeLU output (the 16-bit FFN intermediate)
+
+In train mode a rounded point passes its gradient straight through: the backward's own 16-bit points (saved activations,
+dctx16, dqkv16 of train.hip / train_attn.hip) are not restated.  The GPU tests use the points listed in their STORE tuple.
+
+``error_map`` turns a kernel output and its reference into one RMS error per slice (a (news, 32-token block, head) cell, or any
+labelling), relative to the RMS of the reference over the whole tensor, plus the map's maximum and its outlier ratio
+(maximum / median): rounding noise spreads evenly over slices, a defect confined to one head or one block does not.
+"""
+from __future__ import annotations
+
+from typing import Callable, Dict, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import manner_oracle as O
+
+DT16 = {"f16": torch.float16, "bf16": torch.bfloat16}
+STORE_POINTS = ("qkv", "probs", "ctx", "inter")
+MIN_SLICE = 128                      # elements below which a slice's RMS is too unstable to stand alone
+MAX_THREADS = 16
+
+
+def limit_threads() -> None:
+    if torch.get_num_threads() > MAX_THREADS:
+        torch.set_num_threads(MAX_THREADS)
+
+
+def operands(w: Dict[str, object], mode: Optional[str], device="cpu") -> Dict[str, torch.Tensor]:
+    """The weights as the kernels consume them, in float64: matrices and tables rounded to ``mode``'s 16-bit type first."""
+    out = {}
+    for k, v in w.items():
+        t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v.detach().cpu()).float()
+        if mode is not None and t.dim() == 2:
+            t = t.to(DT16[mode]).float()
+        out[k] = t.double().to(device)
+    return out
+
+
+def _rounder(mode: Optional[str], store: Sequence[str]) -> Callable[[torch.Tensor, str], torch.Tensor]:
+    unknown = set(store) - set(STORE_POINTS)
+    assert not unknown, unknown
+    assert mode is not None or not store, "storage rounding needs a 16-bit mode"
+    pts = frozenset(store)
+
+    def rnd(t, point):
+        if point not in pts:
+            return t
+        return t + (t.to(DT16[mode]).to(t.dtype) - t).detach()          # straight-through in train mode
+    return rnd
+
+
+def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str] = (), train: bool = False, R=None,
+              p_hidden: float = 0.0, p_attn: float = 0.0, p_out: float = 0.0, keep=None, device="cpu", grad_keys=None) -> dict:
+    """Float64 encoder over ``cfg.layers`` layers.
+
+    Inference (``train=False``): {"hidden": [hidden_states[0..layers]] each [N, L, H], "cls": [N, H]}.
+    Train (``train=True``): the reference of train.encode_train — the dropout sites of manner_oracle.encode_cls_train with
+    ``keep(site, kind)`` replaying the kernels' masks — and autograd of (out * R).sum(): {"cls": [N, H], "grads": {name: grad}}
+    over ``grad_keys`` (default: every tensor).  Results are float64 tensors on ``device``."""
+    limit_threads()
+    ids, mask = O._t(ids).long().to(device), O._t(mask).to(device)
+    p = O.bert_named(operands(w, mode, device), cfg)
+    if train:
+        for k in (p if grad_keys is None else grad_keys):
+            p[k].requires_grad_(True)
+    rnd = _rounder(mode, store)
+    n, s = ids.shape
+    h, a, d = cfg.hidden, cfg.heads, cfg.head_dim
+
+    def drop(x, prob, site, kind):
+        if not train or prob <= 0.0:
+            return x
+        return x * keep(site, kind).to(device=device, dtype=x.dtype) / (1.0 - prob)
+
+    add_mask = torch.zeros(mask.shape, dtype=torch.float64, device=device)
+    add_mask = add_mask.masked_fill(mask == 0, torch.finfo(torch.float32).min)[:, None, None, :]
+    with torch.set_grad_enabled(train):
+        x = drop(O.embeddings(ids, p, cfg), p_hidden, 0, "rows")
+        hidden = [x]
+        for l in range(cfg.layers):
+            pre = f"encoder.layer.{l}."
+
+            def lin(t, name):
+                return F.linear(t, p[pre + name + ".weight"], p[pre + name + ".bias"])
+
+            q, k, v = (rnd(lin(x, f"attention.self.{m}"), "qkv").view(n, s, a, d).transpose(1, 2) for m in ("query", "key", "value"))
+            att = F.softmax(torch.matmul(q, k.transpose(2, 3)) * (d ** -0.5) + add_mask, dim=-1)
+            att = rnd(drop(att, p_attn, 8 * (l + 1), "attn"), "probs")
+            ctx = rnd(torch.matmul(att, v).transpose(1, 2).reshape(n, s, h), "ctx")
+            x = F.layer_norm(drop(lin(ctx, "attention.output.dense"), p_hidden, 8 * (l + 1) + 1, "rows") + x, (h,),
+                             p[pre + "attention.output.LayerNorm.weight"], p[pre + "attention.output.LayerNorm.bias"], cfg.ln_eps)
+            inter = rnd(F.gelu(lin(x, "intermediate.dense")), "inter")
+            x = F.layer_norm(drop(lin(inter, "output.dense"), p_hidden, 8 * (l + 1) + 2, "rows") + x, (h,),
+                             p[pre + "output.LayerNorm.weight"], p[pre + "output.LayerNorm.bias"], cfg.ln_eps)
+            hidden.append(x)
+        cls = drop(x[:, 0, :], p_out, 1, "cls")
+        if not train:
+            return {"hidden": hidden, "cls": cls}
+        (cls * O._t(R).to(device=device, dtype=torch.float64)).sum().backward()
+    return {"cls": cls.detach(), "grads": {k: (None if t.grad is None else t.grad) for k, t in p.items() if t.requires_grad}}
+
+
+# ------------------------------------------------------------------------------------------------ labellings
+def token_block_head_labels(mask: np.ndarray, hidden: int, heads: int, block: int = 32) -> np.ndarray:
+    """[N, L, H] int64: one label per (news, head, token block) over the real tokens, -1 on padding.  Labels run over blocks
+    fastest, so a short last block merges with the block before it in the same news and head."""
+    mask = np.asarray(mask)
+    n, lp = mask.shape
+    nb = (lp + block - 1) // block
+    news = np.arange(n)[:, None, None]
+    blk = (np.arange(lp) // block)[None, :, None]
+    head = (np.arange(hidden) // (hidden // heads))[None, None, :]
+    lab = (news * heads + head) * nb + blk
+    return np.where(mask[:, :, None] != 0, lab, -1).astype(np.int64)
+
+
+def news_labels(n: int, hidden: int) -> np.ndarray:
+    """[N, H]: one slice per news (the [CLS] outputs)."""
+    return np.repeat(np.arange(n, dtype=np.int64)[:, None], hidden, 1)
+
+
+def head_row_labels(shape, heads: int) -> np.ndarray:
+    """A [H_out, ...] projection weight or [H_out] bias: one slice per head (rows 64h .. 64h+63)."""
+    rows = np.arange(shape[0]) // (shape[0] // heads)
+    return np.broadcast_to(rows.reshape((-1,) + (1,) * (len(shape) - 1)), shape).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ the map
+class SliceMap(dict):
+    """rms: per-slice RMS error / RMS(reference); labels: the first label of each (merged) slice; max, median, ratio, worst."""
+
+    def __repr__(self):
+        return f"SliceMap(max={self['max']:.3e}, median={self['median']:.3e}, ratio={self['ratio']:.2f}, worst={self['worst']}, n={len(self['rms'])})"
+
+
+def error_map(hip, ref, labels, min_count: int = MIN_SLICE, per_slice: bool = False, floor: float = 1e-2) -> SliceMap:
+    """Per-slice RMS of (hip - ref) over the elements of each label (>= 0; -1 is left out), divided by the RMS of ``ref`` over all
+    labelled elements.  Slices of fewer than ``min_count`` elements are merged into the slice of the next lower label (the first
+    one into the next higher), so the labelling decides who a slice's neighbour is.
+
+    ``per_slice``: divide each slice by the RMS of ``ref`` over that slice instead (at least ``floor`` x the whole tensor's RMS), for
+    tensors whose slices differ in scale by construction — a gradient row of a token in a 31-token news is an order of magnitude
+    larger than one in a 512-token news, and 16-bit rounding noise scales with it."""
+    hip = np.asarray(hip.detach().cpu() if isinstance(hip, torch.Tensor) else hip, dtype=np.float64)
+    ref = np.asarray(ref.detach().cpu() if isinstance(ref, torch.Tensor) else ref, dtype=np.float64)
+    labels = np.broadcast_to(np.asarray(labels), ref.shape)
+    assert hip.shape == ref.shape, (hip.shape, ref.shape)
+    sel = labels >= 0
+    lab, e, r = labels[sel], (hip - ref)[sel], ref[sel]
+    assert np.isfinite(e).all(), "non-finite kernel output"
+    scale = float(np.sqrt(np.mean(r * r)))
+    assert scale > 0.0, "all-zero reference"
+    uniq, inv = np.unique(lab, return_inverse=True)
+    cnt = np.bincount(inv).astype(np.float64)
+    sq = np.bincount(inv, weights=e * e)
+    rq = np.bincount(inv, weights=r * r)
+    groups = []                                            # [first label, count, error sum of squares, reference sum of squares]
+    for u, c, s, q in zip(uniq, cnt, sq, rq):
+        if groups and (groups[-1][1] < min_count or c < min_count):   # the slice before is still too small, or this one is: merge
+            groups[-1][1] += c
+            groups[-1][2] += s
+            groups[-1][3] += q
+        else:
+            groups.append([int(u), c, s, q])
+    rms = np.array([np.sqrt(s / c) / (max(np.sqrt(q / c), floor * scale) if per_slice else scale) for _, c, s, q in groups])
+    med = float(np.median(rms))
+    i = int(np.argmax(rms))
+    return SliceMap(rms=rms, labels=np.array([g[0] for g in groups]), max=float(rms[i]), median=med,
+                    ratio=float(rms[i] / med) if med > 0 else float("inf"), worst=int(groups[i][0]))
