@@ -593,6 +593,33 @@ int manner_hip_news_cache_lookup(const uint64_t* keys, int64_t n_news, uint64_t*
                                  int32_t* row_count, int32_t capacity_rows, int32_t* rows_out, int32_t* state_out, int32_t* scratch,
                                  manner_hip_stream_t stream);
 
+/* ---- token-packed payload of the frozen-prefix cache (csrc/cache.hip) --------------------------------------------------------
+ * The hidden states of a news after the frozen layers, kept by REAL tokens: a table row (the index manner_hip_news_cache_lookup hands
+ * out) owns row_len tokens of `pool` f32 [pool_tokens, hidden] starting at token row_off, so a news costs len x hidden x 4 bytes at
+ * any padded width up to MANNER_HIP_MAX_LEN_INFER.  Caller-owned device state beside the lookup's: pool, row_off int64 [capacity_rows],
+ * row_len int32 [capacity_rows] (filled with -1 = empty; -2 = key known, the pool had no room: no payload, ever; >= 1 = tokens),
+ * row_src int32 [capacity_rows] (scratch), tok_count uint64 [1] (zeroed; tokens handed out — it may come to rest past pool_tokens when
+ * the pool fills, nothing is ever written or read past the pool).  pool, fresh and out are 16-byte aligned, hidden % 4 == 0.  One
+ * stream at a time per table; no call reads anything back to the host.
+ * manner_hip_prefix_resolve: after the lookup — a state-0 row whose key has no payload becomes state 2, row -1 (encode, do not store).
+ * manner_hip_prefix_store: fresh [n_new, padded_len, hidden] = encode_hidden of the rows with state != 0; fresh row j is row index[j]
+ *   of the call (index NULL: j; n_new <= n_news), whose rows / state / lens (real tokens) are [n_news].  Every state-1 row reserves
+ *   its tokens with one device-scope atomic add (correct for any order of the workgroups) and its real tokens are copied; a row that
+ *   does not fit gets row_len -2.  src_of int32 [n_news] receives j at index[j] (for the gather of the same call).
+ * manner_hip_prefix_gather: out [n_news, padded_len, hidden] — a row with a payload: its tokens, zeros at every padded position
+ *   (whatever width it was stored at); a row without one: copied from `fresh` (its own row for state != 0, the row of the state-1
+ *   occurrence of its key for state 0) when `fresh` is given, left untouched for the caller when fresh is NULL. */
+int manner_hip_prefix_resolve(int32_t* rows, int32_t* state, int64_t n_news, const int32_t* row_len, int32_t capacity_rows,
+                              manner_hip_stream_t stream);
+int manner_hip_prefix_store(const float* fresh, int64_t n_new, const int64_t* index, int64_t n_news, const int32_t* rows,
+                            const int32_t* state, const int32_t* lens, int64_t padded_len, int32_t hidden, float* pool,
+                            int64_t pool_tokens, int32_t capacity_rows, int64_t* row_off, int32_t* row_len, int32_t* row_src,
+                            uint64_t* tok_count, int32_t* src_of, manner_hip_stream_t stream);
+int manner_hip_prefix_gather(const int32_t* rows, const int32_t* state, int64_t n_news, int64_t padded_len, int32_t hidden,
+                             const float* pool, int64_t pool_tokens, int32_t capacity_rows, const int64_t* row_off,
+                             const int32_t* row_len, const int32_t* row_src, const float* fresh, int64_t n_fresh,
+                             const int32_t* src_of, float* out, manner_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,9 @@ SIGNATURES = {
     "manner_hip_to_dense": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _P]),
     "manner_hip_news_key128": (C.c_int, [_P, _P, _I64, _I64, _P, _P]),
     "manner_hip_news_cache_lookup": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
+    "manner_hip_prefix_resolve": (C.c_int, [_P, _P, _I64, _P, _I32, _P]),
+    "manner_hip_prefix_store": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "manner_hip_prefix_gather": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "manner_hip_zscore_fuse": (C.c_int, [_P, _I64, _I32, C.POINTER(C.c_float), _P, _I64, _P, _P, _P]),
     "manner_hip_rank_ndcg": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P]),
     "manner_hip_score_fuse_rank_workspace_bytes": (_SZ, [_I32, _I64]),

@@ -505,6 +505,99 @@ class PrefixCache(NewsEmbeddingCache):
             raise
 
 
+def _hash_slots(capacity_rows: int) -> int:
+    n_slots = 2
+    while n_slots < 2 * int(capacity_rows):
+        n_slots *= 2
+    return n_slots
+
+
+def prefix_cache_bytes(hidden: int, capacity_rows: int, pool_tokens: Optional[int] = None, max_len: Optional[int] = None) -> Dict[str, int]:
+    """Device bytes of a frozen-prefix cache, by part.  ``pool_tokens``: a ``PackedPrefixCache`` — payload pool_tokens x hidden f32,
+    16 bytes of row metadata per row (token offset int64, token count and a scratch word int32) + the 8-byte token counter;
+    ``max_len``: a ``PrefixCache`` — payload capacity_rows x max_len x hidden f32.  Both: hash slots of 20 bytes (128-bit key +
+    row), twice the rows rounded up to a power of two, + the 4-byte row counter."""
+    if (pool_tokens is None) == (max_len is None):
+        raise ValueError("prefix_cache_bytes: give pool_tokens (packed) or max_len (padded)")
+    slots = _hash_slots(capacity_rows) * 20 + 4
+    if pool_tokens is not None:
+        payload, rows = int(pool_tokens) * int(hidden) * 4, int(capacity_rows) * 16 + 8
+    else:
+        payload, rows = int(capacity_rows) * int(max_len) * int(hidden) * 4, 0
+    return {"payload": payload, "rows": rows, "slots": slots, "total": payload + rows + slots}
+
+
+class PackedPrefixCache(NewsEmbeddingCache):
+    """``PrefixCache`` with the payload kept by REAL tokens (csrc/cache.hip, manner_hip_prefix_*): a news costs len x hidden f32 in a
+    pool of ``pool_tokens`` token rows instead of a fixed max_len x hidden row, and a batch of any padded width up to
+    ``_lib.MAX_LEN_INFER`` (512) is served — a payload stored at one width gathers into any other that holds the row.  With the
+    title+abstract profile of ``synth.synth_lengths`` capped at 512 (65 238 news, seed 42) the pool needs 5 863 594 tokens, 89.9 per
+    news (276 KB): ``prefix_cache_bytes(768, 65238, 5863594)`` is 18.02 GB against 102.61 GB for rows of 512 — 5.70x less
+    (161 013 news: 44.4 GB against 253.3 GB).  When the pool is full a news keeps
+    its key but gets no payload: it is encoded at every call, as with a full table.  Store and gather are HIP copies of the real
+    tokens; the one host read is the count of rows to encode."""
+
+    def __init__(self, hidden: int, capacity_rows: int, pool_tokens: int, device: torch.device, pool: Optional[Tensor] = None):
+        if int(pool_tokens) < 1 or int(hidden) % 4:
+            raise ValueError("PackedPrefixCache: pool_tokens must be positive and hidden a multiple of 4")
+        super().__init__(0, capacity_rows, device)                 # keys, hash slots and row numbers; no fixed-width table
+        self.hidden, self.pool_tokens, self.max_len = int(hidden), int(pool_tokens), _lib.MAX_LEN_INFER
+        with torch.inference_mode(False):
+            if pool is None:
+                pool = torch.empty((self.pool_tokens, self.hidden), dtype=torch.float32, device=self.device)
+            if pool.dtype != torch.float32 or tuple(pool.shape) != (self.pool_tokens, self.hidden) or not pool.is_contiguous() \
+                    or pool.device != self.table.device or pool.data_ptr() % 16:
+                raise ValueError("PackedPrefixCache: pool must be a contiguous, 16-byte aligned f32 [pool_tokens, hidden] on the device")
+            self.pool = pool
+            self.row_off = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+            self.row_len = torch.full((self.capacity,), -1, dtype=torch.int32, device=self.device)
+            self.row_src = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+            self.tok_count = torch.zeros(1, dtype=torch.int64, device=self.device)                # uint64 bit pattern
+
+    def clear(self) -> None:
+        super().clear()
+        self.row_len.fill_(-1)
+        self.tok_count.zero_()
+
+    def hidden_states(self, engine: "HipEncoder", ids: Tensor, mask: Tensor, n_layers: int, precision: str) -> Tensor:
+        """``engine.encode_hidden(ids, mask, n_layers)`` [N, Lp, H] f32 with every row whose tokens were seen before (and fitted the
+        pool) gathered from the pool — the same bits, zeros at padded positions.  Only batches wider than 512 bypass it."""
+        n, lp = ids.shape
+        if lp > self.max_len or n == 0:
+            return engine.encode_hidden(ids, mask, n_layers, precision=precision)
+        try:
+            lib = _lib.load()
+            rows, state = self.lookup(ids, mask)
+            with torch.cuda.device(rows.device):
+                _lib.check(lib.manner_hip_prefix_resolve(_ptr(rows), _ptr(state), n, _ptr(self.row_len), self.capacity, _stream()))
+            todo = torch.nonzero(state != 0).squeeze(1)                          # one host read: how many rows are new
+            self.lookups += int(n)
+            self.encoded += int(todo.numel())
+            fresh, n_fresh = None, int(todo.numel())
+            src_of = torch.empty(n, dtype=torch.int32, device=rows.device)
+            if n_fresh:
+                whole = n_fresh == n
+                fresh = engine.encode_hidden(ids if whole else ids.index_select(0, todo), mask if whole else mask.index_select(0, todo),
+                                             n_layers, precision=precision)
+                lens = mask.sum(1, dtype=torch.int32)
+                with torch.cuda.device(rows.device):
+                    _lib.check(lib.manner_hip_prefix_store(_ptr(fresh), n_fresh, _ptr(None if whole else todo), n, _ptr(rows), _ptr(state),
+                                                           _ptr(lens), lp, self.hidden, _ptr(self.pool), self.pool_tokens, self.capacity,
+                                                           _ptr(self.row_off), _ptr(self.row_len), _ptr(self.row_src),
+                                                           _ptr(self.tok_count), _ptr(src_of), _stream()))
+                if whole:
+                    return fresh
+            out = torch.empty((n, lp, self.hidden), dtype=torch.float32, device=rows.device)
+            with torch.cuda.device(rows.device):
+                _lib.check(lib.manner_hip_prefix_gather(_ptr(rows), _ptr(state), n, lp, self.hidden, _ptr(self.pool), self.pool_tokens,
+                                                        self.capacity, _ptr(self.row_off), _ptr(self.row_len), _ptr(self.row_src),
+                                                        _ptr(fresh), n_fresh, _ptr(src_of), _ptr(out), _stream()))
+            return out
+        except BaseException:                  # a claimed key without its payload must not survive
+            self.clear()
+            raise
+
+
 def additive_pool(x: Tensor, lin_w: Tensor, lin_b: Tensor, query: Tensor, strict: bool = False) -> Tensor:
     """AdditiveAttention.forward (reference attention.py:21-27).  Default: the one-pass kernel where the shape allows it (D = 768,
     S <= 128, Q <= 320) — x read once and kept on the CU as power-of-two-scaled IEEE-half hi/lo pairs, logits as split (x3) products

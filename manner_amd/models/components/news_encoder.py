@@ -388,10 +388,16 @@ class MannerTextEncoder(nn.Module):
             start = train.first_trainable_layer(plm.cfg, params)
             if 0 < start:
                 pc = getattr(self, "_prefix_cache", None)
-                want = (self.prefix_cache_rows, self.prefix_cache_len, str(ids.device), self._hip_prefix_key)
+                packed = self.prefix_cache_tokens > 0          # payload by real tokens, any padded width up to 512 (hip.PackedPrefixCache)
+                shape = (self.prefix_cache_rows, ("tokens", self.prefix_cache_tokens) if packed else self.prefix_cache_len, str(ids.device))
+                want = shape + (self._hip_prefix_key,)
                 if pc is None or self._prefix_cache_key != want:
-                    if pc is not None and (pc.capacity, pc.max_len, str(pc.device)) == want[:3]:
+                    if pc is not None and self._prefix_cache_key is not None and self._prefix_cache_key[:3] == shape:
                         pc.clear()                                   # same table, other frozen weights / precision
+                    elif packed:
+                        pc = self._prefix_cache = None               # the old payload goes before the new pool is allocated
+                        pc = self._prefix_cache = hip.PackedPrefixCache(plm.cfg.hidden, self.prefix_cache_rows, self.prefix_cache_tokens,
+                                                                        ids.device)
                     else:
                         pc = self._prefix_cache = hip.PrefixCache(plm.cfg.hidden, self.prefix_cache_len, self.prefix_cache_rows, ids.device)
                     self._prefix_cache_key = want
@@ -411,6 +417,10 @@ class MannerTextEncoder(nn.Module):
     #: embeddings and a prefix of layers are frozen.  One row is prefix_cache_len x hidden f32 (96 x 768: 295 KB).
     prefix_cache_rows: int = int(os.environ.get("MANNER_PREFIX_CACHE_ROWS", "0"))
     prefix_cache_len: int = int(os.environ.get("MANNER_PREFIX_CACHE_LEN", "96"))       # tokenizer_max_length, configs/data/mind_rec.yaml:41
+    #: Opt-in on top of prefix_cache_rows: token rows of a `hip.PackedPrefixCache` pool.  0 (the default) keeps the fixed-width table
+    #: above, which batches wider than prefix_cache_len bypass.  Positive: a news costs its real tokens x hidden f32 and batches of
+    #: any width train_max_length admits (up to 512) are cached; prefix_cache_len is not used.  Size it as the pool's total tokens.
+    prefix_cache_tokens: int = int(os.environ.get("MANNER_PREFIX_CACHE_TOKENS", "0"))
 
     def forward(self, tokenized_text) -> torch.Tensor:
         ids, mask = tokenized_text["input_ids"], tokenized_text["attention_mask"]
