@@ -1,5 +1,6 @@
 """Float64 reference of the encoder and per-slice error maps for the 16-bit attention tests (test_attention_slices_host.py,
-test_gpu_attention_slices.py).  A helper module, not a conftest.
+test_gpu_attention_slices.py) and the GEMM tile tests (test_gemm_tiles_host.py, test_gpu_gemm_tiles.py).  A helper module, not a
+conftest.
 
 ``reference`` restates the oracle's encoder (manner_oracle.encode_tokens / encode_cls_train, whose embedding function it calls)
 in float64, on the operands the 16-bit kernels consume: every weight matrix and embedding table rounded to the mode's 16-bit type
@@ -137,6 +138,29 @@ def head_row_labels(shape, heads: int) -> np.ndarray:
     """A [H_out, ...] projection weight or [H_out] bias: one slice per head (rows 64h .. 64h+63)."""
     rows = np.arange(shape[0]) // (shape[0] // heads)
     return np.broadcast_to(rows.reshape((-1,) + (1,) * (len(shape) - 1)), shape).astype(np.int64)
+
+
+def packed_tile_labels(mask: np.ndarray, hidden: int, rows: int = 64, cols: int = 64) -> np.ndarray:
+    """[N, L, H] int64: (packed_row // rows) * (hidden // cols) + col // cols over the real tokens, -1 on padding.  packed_row is
+    the running count of real tokens in news order: the row the GEMMs see when the call is one chunk.  64 x 64 divides the 256- and
+    192-row panels, the 256-column tile and the 128 x 64 wave tile of the persistent GEMMs."""
+    mask = np.asarray(mask) != 0
+    assert hidden % cols == 0, (hidden, cols)
+    row = (np.cumsum(mask.ravel()) - 1).reshape(mask.shape)
+    lab = (row // rows)[:, :, None] * (hidden // cols) + (np.arange(hidden) // cols)[None, None, :]
+    return np.where(mask[:, :, None], lab, -1).astype(np.int64)
+
+
+def weight_tile_labels(shape, tn: int = 128, tk: int = 64) -> np.ndarray:
+    """An [N, K] weight gradient: one slice per tn x tk block, the wave tiles of the 256 x 256 wgrad_tr_kernel tile and of the
+    data-gradient GEMMs.  Labels run over K blocks fastest."""
+    n, k = shape
+    return ((np.arange(n) // tn)[:, None] * ((k + tk - 1) // tk) + (np.arange(k) // tk)[None, :]).astype(np.int64)
+
+
+def vector_block_labels(n: int, block: int = 64) -> np.ndarray:
+    """A bias or LayerNorm gamma / beta gradient: one slice per ``block`` elements (use with min_count=block, per_slice=True)."""
+    return (np.arange(n) // block).astype(np.int64)
 
 
 # ------------------------------------------------------------------------------------------------ the map
