@@ -41,7 +41,7 @@ enum {
  * NULL) and continue on a safe substitute.  The reference raises a Python exception in each of these cases. */
 enum {
   MANNER_HIP_STATUS_MASK = 1,     /* attention_mask is not a right-padded 0/1 prefix with 1..MAX_LEN_INFER tokens (inference),
-                                     1..MAX_LEN_TRAIN tokens (train_forward / _backward) or 1..MAX_LEN tokens ("full rows") */
+                                     1..MAX_LEN_TRAIN tokens (train_forward / _backward) or 1..MAX_LEN_FULL tokens ("full rows") */
   MANNER_HIP_STATUS_TOKEN = 2,    /* input id / position outside the embedding tables (IndexError in the reference) */
   MANNER_HIP_STATUS_FUSED = 4,    /* reserved (bounded-wait overflow of a fused kernel) */
   MANNER_HIP_STATUS_INDEX = 8,    /* news / entity index outside the table (IndexError in the reference) */
@@ -163,14 +163,17 @@ int manner_hip_encoder_status(manner_hip_encoder_t enc, manner_hip_stream_t stre
  * both on `stream`; the caller reads *host_flag once an event recorded after this call has completed.  This is how
  * the module mirror surfaces bad inputs of call k at call k+1 without a host synchronisation per forward. */
 int manner_hip_encoder_status_async(manner_hip_encoder_t enc, int32_t* host_flag /*pinned host*/, manner_hip_stream_t stream);
-/* Per-row token limits.  MANNER_HIP_MAX_LEN: the "full rows" entry points (manner_hip_encode_full, manner_hip_train_full_*) and
- * the short-row attention tile (at most four 32-key tiles per wave).  MANNER_HIP_MAX_LEN_INFER: the inference entry points
- * manner_hip_encode_cls / manner_hip_encode_hidden, whose rows of 129..512 tokens run the long-row attention kernels.
- * MANNER_HIP_MAX_LEN_TRAIN: manner_hip_train_forward / _backward, whose rows of 129..512 tokens run the long-row training
- * attention kernels (the rows of <= 128 tokens keep the short-row kernels and their bits). */
+/* Per-row token limits.  MANNER_HIP_MAX_LEN: the short-row attention tile (at most four 32-key tiles per wave).
+ * MANNER_HIP_MAX_LEN_INFER: the inference entry points manner_hip_encode_cls / manner_hip_encode_hidden, whose rows of 129..512
+ * tokens run the long-row attention kernels.  MANNER_HIP_MAX_LEN_TRAIN: manner_hip_train_forward / _backward, whose rows of
+ * 129..512 tokens run the long-row training attention kernels (the rows of <= 128 tokens keep the short-row kernels and their bits).
+ * MANNER_HIP_MAX_LEN_FULL: the "full rows" entry points (manner_hip_encode_full, manner_hip_train_full_*), padded_len <= 512; a
+ * batch of more than 128 positions runs the row-block grid of the f32 attention kernels (fp32 mode) or the long-row matrix-pipe
+ * kernels with a key count per news (f16 / bf16, head_dim 64); batches of <= 128 positions keep their kernels and their bits. */
 #define MANNER_HIP_MAX_LEN 128
 #define MANNER_HIP_MAX_LEN_INFER 512
 #define MANNER_HIP_MAX_LEN_TRAIN 512
+#define MANNER_HIP_MAX_LEN_FULL 512
 
 /* ABI v8 — sampled fingerprint of a set of tensors, for hosts that cache copies of caller-owned parameters (the module mirror's
  * inference handle packs the PLM weights once; torch's version counters do not see a write through `p.data`).  out[i] = a 32-bit
@@ -483,8 +486,12 @@ int manner_hip_dropout_mask(uint64_t seed, uint32_t site, float p, int64_t n, ui
  * nrms_plm_module.py:119-135): every position of the padded batch is a row (m = n_news * padded_len), the real tokens
  * of a news are its attention keys, padded positions embed the pad token (RoBERTa: at position pad_id) and still
  * produce outputs, no layer is pruned to the [CLS] rows.  hidden / grad_hidden: f32 [n_news * padded_len, H] (row
- * n * padded_len + t); padded_len <= MANNER_HIP_MAX_LEN (128).  saved: manner_hip_train_saved_bytes(cfg, n_news, M, 0), workspace:
- * manner_hip_train_workspace_bytes(cfg, M), M = n_news * padded_len rounded up to 256.  Dropout sites and the grads
+ * n * padded_len + t); padded_len <= MANNER_HIP_MAX_LEN_FULL (512), and every position must fit the model's position table
+ * (MANNER_HIP_STATUS_TOKEN otherwise).  saved: manner_hip_train_saved_bytes(cfg, n_news, M, 0) (the upper bound of every layout),
+ * workspace: manner_hip_train_workspace_bytes(cfg, M), M = n_news * padded_len rounded up to 256 — both per token, nothing of
+ * size padded_len x padded_len is stored.  In f16 / bf16 a batch of more than 128 positions runs the long-row matrix-pipe
+ * attention (queries = every position, keys = the real tokens; MANNER_HIP_TRAIN_ATTN_VALU=1 keeps the f32 kernels); the layout
+ * word of the forward says which, and the backward follows it.  Dropout sites and the grads
  * table as in manner_hip_train_forward / _backward (there is no [CLS] dropout here: the caller owns what follows). */
 int manner_hip_train_full_forward(const manner_hip_encoder_config* cfg, const float* const* weights /*host*/, int32_t n_weights,
                                   const int64_t* ids, const int64_t* mask, int64_t n_news, int64_t padded_len, int32_t precision,
@@ -561,7 +568,9 @@ int manner_hip_dropout(const float* x, float* out, int64_t n, uint64_t seed, uin
  * manner_hip_encode_full replaces `self.plm_model(**tokenized_text)[0]` of PLMTextEncoder.forward
  * (manner/models/components/news_encoder.py:158-160): HF last_hidden_state f32 [n_news, padded_len, H] INCLUDING the padded
  * positions — they embed the pad token (RoBERTa: at position pad_id), attend over the real keys only, and the consumer
- * below mixes them into real tokens.  weights / precision / status as manner_hip_train_forward.
+ * below mixes them into real tokens.  weights / precision / status as manner_hip_train_forward; padded_len <=
+ * MANNER_HIP_MAX_LEN_FULL (512), every position within the model's position table (MANNER_HIP_STATUS_TOKEN otherwise).  In
+ * f16 / bf16 a batch of more than 128 positions takes the long-row matrix-pipe forward kernel of the training path (p = 0).
  * manner_hip_mha_axis0 replaces nn.MultiheadAttention(embed_dim=E, num_heads=heads) as the reference calls it —
  * batch_first=False on a [batch, seq, E] tensor, no masks (news_encoder.py:163-165; user_encoder.py:35-37): attention along
  * AXIS 0 of x [L0, B1, E] (across the news / users of the call, independently per position B1), in/out projections included.

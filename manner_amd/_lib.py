@@ -24,7 +24,8 @@ PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "bf16": PREC_BF16, "bf16x3": PR
 W_EMB_COUNT, WL_COUNT = 5, 16
 MAX_LEN = 128             # training path / short-row attention tile (MANNER_HIP_MAX_LEN)
 MAX_LEN_INFER = 512       # encode_cls / encode_hidden (MANNER_HIP_MAX_LEN_INFER)
-MAX_LEN_TRAIN = 512       # train_forward / train_backward (MANNER_HIP_MAX_LEN_TRAIN); "full rows" keep MAX_LEN
+MAX_LEN_TRAIN = 512       # train_forward / train_backward (MANNER_HIP_MAX_LEN_TRAIN)
+MAX_LEN_FULL = 512        # "full rows": encode_full / train_full_forward / _backward (MANNER_HIP_MAX_LEN_FULL)
 PROF_CLASSES = ["lengths", "embed_ln", "gemm_qkv", "attention", "gemm_out", "layernorm", "gemm_ffn1", "gemm_ffn2",
                 "gather_cls", "cls_tail"]
 

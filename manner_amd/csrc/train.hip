@@ -1047,8 +1047,8 @@ struct Ctx {
   Out16 o16(void* p) const { return (p && dt() != DT_F32) ? Out16{p, (int)dt()} : Out16{nullptr, 0}; }
   // 16-bit modes: Q | K | V are kept in the 16-bit type (the f32 slot of the saved buffer, half used) and the attention runs on the
   // matrix pipe (train_attn.hip).  MANNER_HIP_TRAIN_ATTN_VALU=1 keeps the f32 VALU kernels for A/B; the fp32 mode always uses them.
-  // ONE decision per forward, made in setup() (`choose_attn_path`: environment read per call, "full rows" excluded: they need the key
-  // length mask) and RECORDED against the saved buffer; the backward reads the record instead of re-deriving it, because the layout
+  // ONE decision per forward, made in setup() (`choose_attn_path`: environment read per call; "full rows" take the matrix pipe only
+  // at a padded length > MANNER_HIP_MAX_LEN, where the long-row kernels take the key counts) and RECORDED against the saved buffer; the backward reads the record instead of re-deriving it, because the layout
   // of L.qkv (16-bit or f32) follows from it.
   bool attn_mfma = false;
   bool mfma_attn() const { return attn_mfma; }
@@ -1396,10 +1396,13 @@ int pack_qkv_weights(Ctx& t, int l, void* w16 = nullptr) {
 // never seen, e.g. one produced by another process image).
 static std::mutex g_attn_mu;
 static std::unordered_map<const void*, int> g_attn_path;
-static bool choose_attn_path(const manner_hip_encoder_config* c, int32_t precision, bool full) {
+// "full rows": the matrix pipe only for batches of more than MANNER_HIP_MAX_LEN positions (the long-row kernels take the key counts;
+// shorter full-row batches keep the VALU kernels and their bits)
+static bool choose_attn_path(const manner_hip_encoder_config* c, int32_t precision, bool full, int64_t padded_len = 0) {
   const char* v = getenv("MANNER_HIP_TRAIN_ATTN_VALU");                    // read per call: tests compare both paths in one process
   const bool valu = v && *v && *v != '0';
-  return precision != MANNER_HIP_PREC_F32 && !valu && !full && c->hidden == c->heads * 64;   // the MFMA kernels are written for head_dim 64
+  return precision != MANNER_HIP_PREC_F32 && !valu && (!full || padded_len > MANNER_HIP_MAX_LEN) &&
+         c->hidden == c->heads * 64;                                       // the MFMA kernels are written for head_dim 64
 }
 static bool choose_lean(const manner_hip_encoder_config* c, int32_t precision, int64_t Mb, bool mfma) {
   const char* v = getenv("MANNER_HIP_TRAIN_SAVE16");                       // read per call: the tests compare both layouts in one process
@@ -1508,8 +1511,8 @@ int layer_forward(Ctx& t, int l, LayerSaved& L, const float* x_in, float* x_out,
     }
     if ((rc = gemm_tn(t.dt(), t.dt(), EPI_BIAS, x16, qkv_w16, qkv_b, nullptr, L.qkv, t.Mb, 3 * H, H, t.sv.m_total, s))) return rc;
     // lean: the 16-bit rows alone, into the saved slot (half used) — the out-projection GEMM reads them there
-    if (t.lean) { if ((rc = attn_train_mfma_forward(t.dt(), L.qkv, nullptr, L.ctx, L.ml, cu, t.N, cfg->heads, H, (int)t.Lp, da_m, s))) return rc; }
-    else if ((rc = attn_train_mfma_forward(t.dt(), L.qkv, L.ctx, t.wk.h16b, L.ml, cu, t.N, cfg->heads, H, (int)t.Lp, da_m, s))) return rc;
+    if (t.lean) { if ((rc = attn_train_mfma_forward(t.dt(), L.qkv, nullptr, L.ctx, L.ml, cu, t.N, cfg->heads, H, (int)t.Lp, da_m, s, klen))) return rc; }
+    else if ((rc = attn_train_mfma_forward(t.dt(), L.qkv, L.ctx, t.wk.h16b, L.ml, cu, t.N, cfg->heads, H, (int)t.Lp, da_m, s, klen))) return rc;
   } else {
     if ((rc = linear_fwd(t, x_in, t.wk.wcat, t.wk.bcat, L.qkv, 3 * H, H, mixed && x_in_has_16 ? t.wk.h16a : nullptr))) return rc;
     const Drop da = da_m;
@@ -1672,7 +1675,7 @@ int manner_hip_encode_full(const manner_hip_encoder_config* cfg, const float* co
   int rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t Mb = round_up(n_news * padded_len, 256);
-  if ((rc = check_cfg(cfg, n_news, padded_len, Mb, precision, 0, MANNER_HIP_MAX_LEN))) return rc;
+  if ((rc = check_cfg(cfg, n_news, padded_len, Mb, precision, 0, MANNER_HIP_MAX_LEN_FULL))) return rc;
   if (!weights || n_weights != MANNER_HIP_W_EMB_COUNT + cfg->layers * MANNER_HIP_WL_COUNT) return fail(MANNER_HIP_E_INVALID, "encode_full: weight table size");
   for (int i = 0; i < n_weights; ++i)
     if (!weights[i]) return fail(MANNER_HIP_E_INVALID, "encode_full: weight %d is NULL", i);
@@ -1685,11 +1688,12 @@ int manner_hip_encode_full(const manner_hip_encoder_config* cfg, const float* co
   t.c = cfg; t.w = weights; t.N = n_news; t.Lp = padded_len; t.Mb = Mb; t.prec = precision; t.s = s;
   t.wk = f.wk;
   t.sv.lens = f.lens; t.sv.cu = f.cu_full; t.sv.m_total = f.m_total;
+  t.attn_mfma = choose_attn_path(cfg, precision, true, padded_len);   // > 128 positions, 16-bit: the long-row forward kernel (p = 0, no statistics)
   const int H = cfg->hidden;
   const size_t wide = (size_t)(cfg->intermediate > 3 * H ? cfg->intermediate : 3 * H);
   MANNER_HIP_TRY(hipMemsetAsync(t.wk.zero, 0, wide * sizeof(float), s));
   // real lengths (validated like every other entry point) = key counts; rows = every position
-  if ((rc = lengths_and_offsets(mask, n_news, padded_len, f.lens, f.cu_real, f.m_real, Mb, -1, status, s, MANNER_HIP_MAX_LEN))) return rc;
+  if ((rc = lengths_and_offsets(mask, n_news, padded_len, f.lens, f.cu_real, f.m_real, Mb, -1, status, s, MANNER_HIP_MAX_LEN_FULL))) return rc;
   hipLaunchKernelGGL(full_offsets_kernel, dim3((unsigned)((n_news + 256) / 256)), dim3(256), 0, s, f.cu_full, f.m_total, n_news, (int)padded_len);
   MANNER_LAUNCH_CHECK();
   const bool roberta = cfg->arch == MANNER_HIP_ARCH_ROBERTA;
@@ -1720,8 +1724,9 @@ static int train_forward_impl(const manner_hip_encoder_config* cfg, const float*
   int rc;
   hipStream_t s = (hipStream_t)stream;
   // the attention path and the saved-tensor layout are decided BEFORE the buffers are planned (the layout sizes the slots)
-  const bool mfma_rule = cfg && choose_attn_path(cfg, precision, full);
-  const bool lean_rule = cfg && m_bound > 0 && choose_lean(cfg, precision, m_bound, mfma_rule);
+  const bool mfma_rule = cfg && choose_attn_path(cfg, precision, full, padded_len);
+  // "full rows" keep the f32 saved layout on either attention path (their backward is the unpruned all-rows walk)
+  const bool lean_rule = cfg && m_bound > 0 && choose_lean(cfg, precision, m_bound, mfma_rule && !full);
   if ((rc = setup(t, cfg, weights, n_weights, n_news, padded_len, m_bound, precision, start_layer, saved, saved_bytes, workspace,
                   workspace_bytes, s, wc, lean_rule)))
     return rc;
@@ -1740,7 +1745,7 @@ static int train_forward_impl(const manner_hip_encoder_config* cfg, const float*
   if (full) {
     if (start_layer != 0 || m_bound != round_up(n_news * padded_len, 256)) return fail(MANNER_HIP_E_INVALID, "train_full_forward: m_bound must be round_up(n_news * padded_len, 256)");
     // real lengths (validated as everywhere) = key counts; the packed offsets they imply are scratch (wk.dsum / wk.dims)
-    if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, reinterpret_cast<int32_t*>(t.wk.dsum), t.wk.dims + 8, m_bound, -1, status, s, MANNER_HIP_MAX_LEN_TRAIN))) return rc;
+    if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, reinterpret_cast<int32_t*>(t.wk.dsum), t.wk.dims + 8, m_bound, -1, status, s, MANNER_HIP_MAX_LEN_FULL))) return rc;
     hipLaunchKernelGGL(full_offsets_kernel, dim3((unsigned)((n_news + 256) / 256)), dim3(256), 0, s, sv.cu, sv.m_total, n_news, (int)padded_len);
     MANNER_LAUNCH_CHECK();
   } else if ((rc = lengths_and_offsets(mask, n_news, padded_len, sv.lens, sv.cu, sv.m_total, m_bound, -1, status, s, MANNER_HIP_MAX_LEN_TRAIN))) {
@@ -1804,7 +1809,7 @@ static int train_backward_impl(const manner_hip_encoder_config* cfg, const float
   if (!ids || !grad_cls || !grads) return fail(MANNER_HIP_E_INVALID, "train_backward: null pointer");
   t.attn_mfma = mfma_rec;
   t.lean = lean_rec;
-  if (t.attn_mfma && (precision == MANNER_HIP_PREC_F32 || full)) return fail(MANNER_HIP_E_INVALID, "train_backward: the forward of this saved buffer ran another precision / row layout");
+  if ((t.attn_mfma && (precision == MANNER_HIP_PREC_F32 || (full && padded_len <= MANNER_HIP_MAX_LEN))) || (t.lean && full)) return fail(MANNER_HIP_E_INVALID, "train_backward: the forward of this saved buffer ran another precision / row layout");
   if (grad_prefix && start_layer == 0) return fail(MANNER_HIP_E_INVALID, "train_backward: grad_prefix goes with start_layer > 0");
   const int H = cfg->hidden, I = cfg->intermediate;
   Saved& sv = t.sv;
@@ -2014,7 +2019,7 @@ static int train_backward_impl(const manner_hip_encoder_config* cfg, const float
                                            wk.h16a, wk.dsum, sv.cu, n_news, cfg->heads, H, (int)padded_len, da, m_bound, sv.m_total, s)))
           return rc;
       } else if ((rc = attn_train_mfma_backward(t.dt(), L.qkv, wk.dx, false, L.ctx, false, L.ml, wk.dqkv, b_dqkv, wk.h16a, wk.dsum, sv.cu, n_news, cfg->heads, H,
-                                                (int)padded_len, da, m_bound, sv.m_total, s)))
+                                                (int)padded_len, da, m_bound, sv.m_total, s, full ? sv.lens : nullptr)))
         return rc;
     } else {
 #define MANNER_ATTN_BWD(AT_, HPB_)                                                                                              \
@@ -2123,8 +2128,8 @@ int manner_hip_train_full_forward(const manner_hip_encoder_config* cfg, const fl
                                   float p_hidden, float p_attn, uint64_t seed, float* hidden, void* saved, size_t saved_bytes,
                                   void* workspace, size_t workspace_bytes, int32_t* status, manner_hip_stream_t stream) {
   if (n_news <= 0 || padded_len <= 0) return fail(MANNER_HIP_E_INVALID, "train_full_forward: empty batch");
-  if (padded_len > MANNER_HIP_MAX_LEN)
-    return fail(MANNER_HIP_E_INVALID, "train_full_forward: padded_len=%lld (padded_len <= %d)", (long long)padded_len, MANNER_HIP_MAX_LEN);
+  if (padded_len > MANNER_HIP_MAX_LEN_FULL)
+    return fail(MANNER_HIP_E_INVALID, "train_full_forward: padded_len=%lld (padded_len <= %d)", (long long)padded_len, MANNER_HIP_MAX_LEN_FULL);
   return train_forward_impl(cfg, weights, n_weights, ids, mask, n_news, padded_len, round_up(n_news * padded_len, 256), precision, 0, nullptr,
                             p_hidden, p_attn, 0.f, seed, hidden, saved, saved_bytes, workspace, workspace_bytes, status, stream, true);
 }
@@ -2134,8 +2139,8 @@ int manner_hip_train_full_backward(const manner_hip_encoder_config* cfg, const f
                                    float p_attn, uint64_t seed, const float* grad_hidden, void* saved, size_t saved_bytes,
                                    float* const* grads, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream) {
   if (n_news <= 0 || padded_len <= 0) return fail(MANNER_HIP_E_INVALID, "train_full_backward: empty batch");
-  if (padded_len > MANNER_HIP_MAX_LEN)
-    return fail(MANNER_HIP_E_INVALID, "train_full_backward: padded_len=%lld (padded_len <= %d)", (long long)padded_len, MANNER_HIP_MAX_LEN);
+  if (padded_len > MANNER_HIP_MAX_LEN_FULL)
+    return fail(MANNER_HIP_E_INVALID, "train_full_backward: padded_len=%lld (padded_len <= %d)", (long long)padded_len, MANNER_HIP_MAX_LEN_FULL);
   return train_backward_impl(cfg, weights, n_weights, ids, n_news, padded_len, round_up(n_news * padded_len, 256), precision, 0, p_hidden,
                              p_attn, 0.f, seed, grad_hidden, saved, saved_bytes, grads, nullptr, workspace, workspace_bytes, stream, true);
 }

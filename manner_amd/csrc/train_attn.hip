@@ -17,7 +17,9 @@
 // with D_i = dctx_i . ctx_i (= sum_j dP_ij P_ij; ctx carries the same dropout) from a small pre-pass that also writes the
 // 16-bit copy of dctx.  Dropout bits are regenerated from (seed, site, (row * heads + head) * 256 + key) in all three.
 // News of 129 .. 512 tokens (training's MANNER_HIP_MAX_LEN_TRAIN) run the *_long_kernel passes below (one workgroup per news, head
-// and block of rows; the short kernels return at once for them), with a dropout stream of their own (attn_drop_for).
+// and block of rows; the short kernels return at once for them), with a dropout stream of their own (attn_drop_for).  The same
+// passes serve the "full rows" batches of more than 128 positions (KEYS = true: every position of a news is a query, its first
+// klen[n] positions are its keys).
 #include <math.h>
 
 #include <algorithm>
@@ -462,6 +464,13 @@ __global__ __launch_bounds__(256) void attn_train_mfma_bwd_kv_kernel(const TE* _
 //   backward-q  K and V images + eight slabs (8 waves, 256 queries)                                           160 KiB
 //   backward-kv Q and d ctx images + {-max C, 1 / sum, D} per query (12 B a row) + four slabs (4 waves, 128 keys)  150 KiB
 // Dropout: the long-row stream (attn_drop_for / attn_drop_shift); the kernels return at once for a row of <= 128 tokens.
+// KEYS ("full rows", klen != NULL): a news has LQ = L rows, all of them queries (padded positions included: they produce ctx,
+// {m, l} and d q), and LK = klen[n] keys, 1 <= LK <= LQ.  The news is routed, and its dropout stream chosen, by the ROW count LQ (as
+// the VALU kernels do), so a news of 3 real tokens in a batch padded to 300 runs here.  Key side: ceil32(LK) rows of K / V are staged,
+// replicas clamped to LK - 1, keys >= LK masked to -inf (forward) / weighted by 0 (backward) in the one tile that can hold them; the
+// Q / d ctx images of backward-kv stay whole (LQ rows).  Rows LK .. LQ - 1 are no keys: backward-kv WRITES their d k = d v = 0 (d qkv
+// is read whole by the data-gradient GEMM), also from a key block that lies wholly past LK.  KEYS = false compiles LK to L: the
+// kernels of the packed path.
 constexpr int LONG_FWD_WAVES = 8, LONG_Q_WAVES = 8, LONG_KV_WAVES = 4;
 constexpr int LONG_LDS_FWD = MANNER_HIP_MAX_LEN_TRAIN * 256 + LONG_FWD_WAVES * 4096;
 constexpr int LONG_LDS_Q = MANNER_HIP_MAX_LEN_TRAIN * 256 + LONG_Q_WAVES * 4096;
@@ -500,8 +509,10 @@ __device__ __forceinline__ typename E16<TE>::v8 tr_frag_swz(const char* img, int
   return __builtin_bit_cast(typename E16<TE>::v8, both);
 }
 // the (news, head, block) of a long-row workgroup: false (workgroup-uniform) for a short row or a block past the row's end
-__device__ __forceinline__ bool long_block(const int32_t* __restrict__ cu, int64_t n_pairs, int n_blk, int heads, int rows_per_blk,
-                                           int& tok0, int& L, int& head, int& blk) {
+// LK = the news' key count: L itself, or (KEYS) klen[n] clamped into [1, L]
+template <bool KEYS>
+__device__ __forceinline__ bool long_block(const int32_t* __restrict__ cu, const int32_t* __restrict__ klen, int64_t n_pairs, int n_blk,
+                                           int heads, int rows_per_blk, int& tok0, int& L, int& LK, int& head, int& blk) {
   const int64_t pair = (int64_t)blockIdx.x / n_blk;
   blk = (int)((int64_t)blockIdx.x - pair * n_blk);
   if (pair >= n_pairs) return false;
@@ -509,31 +520,34 @@ __device__ __forceinline__ bool long_block(const int32_t* __restrict__ cu, int64
   head = (int)(pair - (int64_t)n * heads);
   tok0 = __builtin_amdgcn_readfirstlane(cu[n]);
   L = __builtin_amdgcn_readfirstlane(cu[n + 1]) - tok0;
+  LK = L;
+  if constexpr (KEYS) LK = max(1, min(__builtin_amdgcn_readfirstlane(klen[n]), L));
   return L > MANNER_HIP_MAX_LEN && rows_per_blk * blk < L;
 }
 
-template <typename TE>
+template <typename TE, bool KEYS>
 __global__ __launch_bounds__(64 * LONG_FWD_WAVES, 1) void attn_train_mfma_fwd_long_kernel(const TE* __restrict__ qkv, float* __restrict__ ctx,
                                                                                          TE* __restrict__ ctx16, float2* __restrict__ ml,
                                                                                          const int32_t* __restrict__ cu, int64_t n_pairs,
-                                                                                         int n_blk, int heads, int H, int rows_cap, Drop drop) {
+                                                                                         int n_blk, int heads, int H, int rows_cap, Drop drop,
+                                                                                         const int32_t* __restrict__ klen) {
   typedef typename E16<TE>::v8 e16x8;
   constexpr int W = LONG_FWD_WAVES;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  int tok0, L, head, blk;
-  if (!long_block(cu, n_pairs, n_blk, heads, 32 * W, tok0, L, head, blk)) return;
+  int tok0, L, LK, head, blk;
+  if (!long_block<KEYS>(cu, klen, n_pairs, n_blk, heads, 32 * W, tok0, L, LK, head, blk)) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
   char* kimg = lds;
   char* vimg = lds + (size_t)rows_cap * 128;
   char* ol = lds + (size_t)rows_cap * 256 + wave * 4096;
   const size_t ld = 3 * (size_t)H;
   const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
-  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;
+  const int nrows = (LK + 31) & ~31, nkt = nrows >> 5;    // key side
   const int q0 = 32 * W * blk + 32 * wave;
   e16x8 qf[4];
   fetch_frags<TE>(Qb, ld, q0, L, ol, qf);
-  dma_image_swz<TE>(Qb + H, ld, L, nrows, kimg, wave, W);
-  dma_image_swz<TE>(Qb + 2 * H, ld, L, nrows, vimg, wave, W);
+  dma_image_swz<TE>(Qb + H, ld, LK, nrows, kimg, wave, W);
+  dma_image_swz<TE>(Qb + 2 * H, ld, LK, nrows, vimg, wave, W);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's share of the images (LDS-DMA is not tracked by the compiler)
   __syncthreads();                                        // ... and every other wave's
   if (q0 >= L) return;                                    // wave-uniform: no query of this wave is real (no barrier follows)
@@ -548,15 +562,15 @@ __global__ __launch_bounds__(64 * LONG_FWD_WAVES, 1) void attn_train_mfma_fwd_lo
     f32x16 st = zero16();
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) st = E16<TE>::mfma32(kf[ks], qf[ks], st);
-    if (32 * kt + 32 > L) {                               // wave-uniform: the last tile holds keys >= L
+    if (32 * kt + 32 > LK) {                              // wave-uniform: a tile that holds keys >= LK
 #pragma unroll
-      for (int e = 0; e < 16; ++e) st[e] = 32 * kt + acc_row(e, h) < L ? st[e] : -INFINITY;
+      for (int e = 0; e < 16; ++e) st[e] = 32 * kt + acc_row(e, h) < LK ? st[e] : -INFINITY;
     }
     float tmx = st[0];
 #pragma unroll
     for (int e = 1; e < 16; ++e) tmx = fmaxf(tmx, st[e]);
     tmx = fmaxf(tmx, __shfl_xor(tmx, 32, 64));
-    const float mn = fmaxf(m, tmx);                       // finite: tile 0 always holds key 0 < L
+    const float mn = fmaxf(m, tmx);                       // finite: tile 0 always holds key 0 < LK
     const float nmc = -mn * kC;
     float rs = 0.f;
     e16x8 pf[2];
@@ -585,20 +599,22 @@ __global__ __launch_bounds__(64 * LONG_FWD_WAVES, 1) void attn_train_mfma_fwd_lo
   }
   store_rows<TE>(ol, o, 1.0f / l, q0, L, ctx ? ctx + (size_t)tok0 * H + head * 64 : nullptr, (size_t)H,
                  ctx16 ? ctx16 + (size_t)tok0 * H + head * 64 : nullptr, (size_t)H);
+  if constexpr (KEYS) { if (!ml) return; }                // inference over full rows (manner_hip_encode_full) keeps no statistics
   if (h == 0 && q < L) ml[(size_t)(tok0 + q) * heads + head] = float2{m, l};
 }
 
-template <typename TE>
+template <typename TE, bool KEYS>
 __global__ __launch_bounds__(64 * LONG_Q_WAVES, 1) void attn_train_mfma_bwd_q_long_kernel(const TE* __restrict__ qkv, const TE* __restrict__ dctx16,
                                                                                          const float2* __restrict__ ml, const float* __restrict__ dsum,
                                                                                          float* __restrict__ dqkv, TE* __restrict__ dqkv16,
                                                                                          const int32_t* __restrict__ cu, int64_t n_pairs,
-                                                                                         int n_blk, int heads, int H, int rows_cap, Drop drop) {
+                                                                                         int n_blk, int heads, int H, int rows_cap, Drop drop,
+                                                                                         const int32_t* __restrict__ klen) {
   typedef typename E16<TE>::v8 e16x8;
   constexpr int W = LONG_Q_WAVES;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  int tok0, L, head, blk;
-  if (!long_block(cu, n_pairs, n_blk, heads, 32 * W, tok0, L, head, blk)) return;
+  int tok0, L, LK, head, blk;
+  if (!long_block<KEYS>(cu, klen, n_pairs, n_blk, heads, 32 * W, tok0, L, LK, head, blk)) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
   char* kimg = lds;
   char* vimg = lds + (size_t)rows_cap * 128;
@@ -606,7 +622,7 @@ __global__ __launch_bounds__(64 * LONG_Q_WAVES, 1) void attn_train_mfma_bwd_q_lo
   const size_t ld = 3 * (size_t)H;
   const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
   const TE* Gb = dctx16 + (size_t)tok0 * H + head * 64;
-  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;
+  const int nrows = (LK + 31) & ~31, nkt = nrows >> 5;    // key side
   const int q0 = 32 * W * blk + 32 * wave;
   e16x8 qf[4], gf[4];
   fetch_frags<TE>(Qb, ld, q0, L, ol, qf);
@@ -615,8 +631,8 @@ __global__ __launch_bounds__(64 * LONG_Q_WAVES, 1) void attn_train_mfma_bwd_q_lo
   const float2 st2 = ml[(size_t)(tok0 + q) * heads + head];
   const float nmc = -st2.x * kC, invl = 1.0f / st2.y;
   const float D = dsum[(size_t)(tok0 + q) * heads + head];
-  dma_image_swz<TE>(Qb + H, ld, L, nrows, kimg, wave, W);
-  dma_image_swz<TE>(Qb + 2 * H, ld, L, nrows, vimg, wave, W);
+  dma_image_swz<TE>(Qb + H, ld, LK, nrows, kimg, wave, W);
+  dma_image_swz<TE>(Qb + 2 * H, ld, LK, nrows, vimg, wave, W);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (q0 >= L) return;
@@ -637,7 +653,7 @@ __global__ __launch_bounds__(64 * LONG_Q_WAVES, 1) void attn_train_mfma_bwd_q_lo
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = 32 * kt + acc_row(e, h);
-      const float p = key < L ? __builtin_amdgcn_exp2f(fmaf(st[e], kC, nmc)) * invl : 0.f;
+      const float p = key < LK ? __builtin_amdgcn_exp2f(fmaf(st[e], kC, nmc)) * invl : 0.f;
       const float g = dr.apply(dp[e], didx0 + (uint64_t)key);
       dsf[e >> 3][e & 7] = (TE)(p * (g - D) * 0.125f);
     }
@@ -650,17 +666,18 @@ __global__ __launch_bounds__(64 * LONG_Q_WAVES, 1) void attn_train_mfma_bwd_q_lo
                  dqkv16 ? dqkv16 + (size_t)tok0 * ld + head * 64 : nullptr, ld);
 }
 
-template <typename TE>
+template <typename TE, bool KEYS>
 __global__ __launch_bounds__(64 * LONG_KV_WAVES, 1) void attn_train_mfma_bwd_kv_long_kernel(const TE* __restrict__ qkv, const TE* __restrict__ dctx16,
                                                                                            const float2* __restrict__ ml, const float* __restrict__ dsum,
                                                                                            float* __restrict__ dqkv, TE* __restrict__ dqkv16,
                                                                                            const int32_t* __restrict__ cu, int64_t n_pairs,
-                                                                                           int n_blk, int heads, int H, int rows_cap, Drop drop) {
+                                                                                           int n_blk, int heads, int H, int rows_cap, Drop drop,
+                                                                                           const int32_t* __restrict__ klen) {
   typedef typename E16<TE>::v8 e16x8;
   constexpr int W = LONG_KV_WAVES;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  int tok0, L, head, blk;
-  if (!long_block(cu, n_pairs, n_blk, heads, 32 * W, tok0, L, head, blk)) return;
+  int tok0, L, LK, head, blk;
+  if (!long_block<KEYS>(cu, klen, n_pairs, n_blk, heads, 32 * W, tok0, L, LK, head, blk)) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rr = lane & 31, h = lane >> 5;
   char* qimg = lds;                                       // Q image, d ctx image, row statistics, slabs
   char* gimg = lds + (size_t)rows_cap * 128;
@@ -671,11 +688,26 @@ __global__ __launch_bounds__(64 * LONG_KV_WAVES, 1) void attn_train_mfma_bwd_kv_
   const size_t ld = 3 * (size_t)H;
   const TE* Qb = qkv + (size_t)tok0 * ld + head * 64;
   const TE* Gb = dctx16 + (size_t)tok0 * H + head * 64;
-  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;
+  const int nrows = (L + 31) & ~31, nkt = nrows >> 5;     // query side: whole (LQ rows)
   const int k0 = 32 * W * blk + 32 * wave;
+  float* const dk32 = dqkv ? dqkv + (size_t)tok0 * ld + H + head * 64 : nullptr;
+  TE* const dk16 = dqkv16 ? dqkv16 + (size_t)tok0 * ld + H + head * 64 : nullptr;
+  if constexpr (KEYS) {
+    // rows k0 .. k0 + 31 are no keys (past LK, inside LQ): their d k = d v = 0 is still written.  A block that lies wholly past LK
+    // (workgroup-uniform) does so without staging anything; a single wave past LK of a block that holds keys joins the staging and
+    // the barrier first, like a wave past the row's end.
+    if (32 * W * blk >= LK) {
+      if (k0 < L) {
+        const f32x16 z[2] = {zero16(), zero16()};
+        store_rows<TE>(ol, z, 1.0f, k0, L, dk32, ld, dk16, ld);
+        store_rows<TE>(ol, z, 1.0f, k0, L, dk32 ? dk32 + H : nullptr, ld, dk16 ? dk16 + H : nullptr, ld);
+      }
+      return;
+    }
+  }
   e16x8 kfb[4], vfb[4];
-  fetch_frags<TE>(Qb + H, ld, k0, L, ol, kfb);
-  fetch_frags<TE>(Qb + 2 * H, ld, k0, L, ol, vfb);
+  fetch_frags<TE>(Qb + H, ld, k0, LK, ol, kfb);
+  fetch_frags<TE>(Qb + 2 * H, ld, k0, LK, ol, vfb);
   dma_image_swz<TE>(Qb, ld, L, nrows, qimg, wave, W);
   dma_image_swz<TE>(Gb, (size_t)H, L, nrows, gimg, wave, W);
   for (int r = threadIdx.x; r < nrows; r += 64 * W) {
@@ -688,6 +720,14 @@ __global__ __launch_bounds__(64 * LONG_KV_WAVES, 1) void attn_train_mfma_bwd_kv_
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (k0 >= L) return;
+  if constexpr (KEYS) {
+    if (k0 >= LK) {                                       // wave-uniform, after the barrier: no key among this wave's rows
+      const f32x16 z[2] = {zero16(), zero16()};
+      store_rows<TE>(ol, z, 1.0f, k0, L, dk32, ld, dk16, ld);
+      store_rows<TE>(ol, z, 1.0f, k0, L, dk32 ? dk32 + H : nullptr, ld, dk16 ? dk16 + H : nullptr, ld);
+      return;
+    }
+  }
   const Drop dr = attn_drop_for(drop, L);
   const int dsh = attn_drop_shift(L);
   const int key = k0 + rr;
@@ -706,7 +746,7 @@ __global__ __launch_bounds__(64 * LONG_KV_WAVES, 1) void attn_train_mfma_bwd_kv_
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int qi = 32 * qt + acc_row(e, h);
-      const float p = qi < L ? __builtin_amdgcn_exp2f(fmaf(s[e], kC, sm[qi])) * sl[qi] : 0.f;
+      const float p = (qi < L && key < LK) ? __builtin_amdgcn_exp2f(fmaf(s[e], kC, sm[qi])) * sl[qi] : 0.f;
       const bool keep = dr.thr == 0 || drop_bits(dr.seed, dr.site, (((uint64_t)(tok0 + qi) * heads + head) << dsh) + (uint64_t)key) >= dr.thr;
       const float pd = keep ? p * dr.scale : 0.f;
       const float g = keep ? dp[e] * dr.scale : 0.f;
@@ -721,10 +761,14 @@ __global__ __launch_bounds__(64 * LONG_KV_WAVES, 1) void attn_train_mfma_bwd_kv_
         dk[dt] = E16<TE>::mfma32(tr_frag_swz<TE>(qimg, qt, s2, dt), dsf[s2], dk[dt]);
       }
   }
-  store_rows<TE>(ol, dk, 1.0f, k0, L, dqkv ? dqkv + (size_t)tok0 * ld + H + head * 64 : nullptr, ld,
-                 dqkv16 ? dqkv16 + (size_t)tok0 * ld + H + head * 64 : nullptr, ld);
-  store_rows<TE>(ol, dv, 1.0f, k0, L, dqkv ? dqkv + (size_t)tok0 * ld + 2 * H + head * 64 : nullptr, ld,
-                 dqkv16 ? dqkv16 + (size_t)tok0 * ld + 2 * H + head * 64 : nullptr, ld);
+  if constexpr (KEYS) {
+    if (key >= LK) {                                      // a lane's column = its key: the rows past LK of the tile that holds LK
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) dk[dt] = dv[dt] = zero16();
+    }
+  }
+  store_rows<TE>(ol, dk, 1.0f, k0, L, dk32, ld, dk16, ld);
+  store_rows<TE>(ol, dv, 1.0f, k0, L, dk32 ? dk32 + H : nullptr, ld, dk16 ? dk16 + H : nullptr, ld);
 }
 
 constexpr int MAX_LDS_FWD = 4 * (4 * 4096 + 4096);                 // 4 waves x (V image of 4 tiles + slab)
@@ -737,11 +781,11 @@ int raise_lds() {
   MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_kv_kernel<TE, NKTMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_KV));
   return MANNER_HIP_OK;
 }
-template <typename TE>
+template <typename TE, bool KEYS>
 int raise_lds_long() {
-  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_fwd_long_kernel<TE>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_FWD));
-  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_q_long_kernel<TE>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_Q));
-  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_kv_long_kernel<TE>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_KV));
+  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_fwd_long_kernel<TE, KEYS>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_FWD));
+  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_q_long_kernel<TE, KEYS>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_Q));
+  MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_train_mfma_bwd_kv_long_kernel<TE, KEYS>), hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_KV));
   return MANNER_HIP_OK;
 }
 int ensure_lds() {
@@ -751,14 +795,17 @@ int ensure_lds() {
     int rc;
     if ((rc = raise_lds<f16_t, 1>()) || (rc = raise_lds<f16_t, 2>()) || (rc = raise_lds<f16_t, 3>()) || (rc = raise_lds<f16_t, 4>()) ||
         (rc = raise_lds<bf16_t, 1>()) || (rc = raise_lds<bf16_t, 2>()) || (rc = raise_lds<bf16_t, 3>()) || (rc = raise_lds<bf16_t, 4>()) ||
-        (rc = raise_lds_long<f16_t>()) || (rc = raise_lds_long<bf16_t>()))
+        (rc = raise_lds_long<f16_t, false>()) || (rc = raise_lds_long<bf16_t, false>()) || (rc = raise_lds_long<f16_t, true>()) ||
+        (rc = raise_lds_long<bf16_t, true>()))
       return rc;
     r = true;
   }
   return MANNER_HIP_OK;
 }
 
-int check_shape(DType dt, int heads, int H, int max_len) {
+int check_shape(DType dt, int heads, int H, int max_len, const int32_t* klen) {
+  if (klen && max_len <= MANNER_HIP_MAX_LEN)
+    return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: key counts go with a padded length > %d (got %d)", MANNER_HIP_MAX_LEN, max_len);
   if (!is_16bit(dt)) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: 16-bit element types only");
   if (H != heads * 64 || H % 8) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma: head_dim must be 64 (H=%d heads=%d)", H, heads);
   if (max_len < 1 || max_len > MANNER_HIP_MAX_LEN_TRAIN)
@@ -785,9 +832,9 @@ LongGrid long_grid(int64_t pairs, int max_len, int W) {
 }  // namespace
 
 int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16, float2* ml, const int32_t* cu, int64_t n_news,
-                            int heads, int H, int max_len, Drop drop, hipStream_t stream) {
+                            int heads, int H, int max_len, Drop drop, hipStream_t stream, const int32_t* klen) {
   int rc;
-  if ((rc = check_shape(dt, heads, H, max_len)) || (rc = ensure_lds())) return rc;
+  if ((rc = check_shape(dt, heads, H, max_len, klen)) || (rc = ensure_lds())) return rc;
   const int64_t pairs = n_news * heads;
   const int nkt = short_tiles(max_len);
   const int lds_per_wave = nkt * 4096 + 4096;
@@ -804,11 +851,11 @@ int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16
   if (max_len > MANNER_HIP_MAX_LEN) {                         // rows of 129 .. max_len tokens (the short kernels skipped them)
     const LongGrid lg = long_grid(pairs, max_len, LONG_FWD_WAVES);
     const size_t lds = (size_t)lg.rows_cap * 256 + LONG_FWD_WAVES * 4096;
-#define MANNER_ATTN_FWD_LONG(TE_)                                                                                                          \
-  hipLaunchKernelGGL(attn_train_mfma_fwd_long_kernel<TE_>, dim3(lg.grid), dim3(64 * LONG_FWD_WAVES), lds, stream, static_cast<const TE_*>(qkv16), \
-                     ctx, static_cast<TE_*>(ctx16), ml, cu, pairs, lg.n_blk, heads, H, lg.rows_cap, drop)
-    if (dt == DT_F16) MANNER_ATTN_FWD_LONG(f16_t);
-    else MANNER_ATTN_FWD_LONG(bf16_t);
+#define MANNER_ATTN_FWD_LONG(TE_, KEYS_)                                                                                                   \
+  hipLaunchKernelGGL((attn_train_mfma_fwd_long_kernel<TE_, KEYS_>), dim3(lg.grid), dim3(64 * LONG_FWD_WAVES), lds, stream,                 \
+                     static_cast<const TE_*>(qkv16), ctx, static_cast<TE_*>(ctx16), ml, cu, pairs, lg.n_blk, heads, H, lg.rows_cap, drop, klen)
+    if (dt == DT_F16) { if (klen) MANNER_ATTN_FWD_LONG(f16_t, true); else MANNER_ATTN_FWD_LONG(f16_t, false); }
+    else { if (klen) MANNER_ATTN_FWD_LONG(bf16_t, true); else MANNER_ATTN_FWD_LONG(bf16_t, false); }
 #undef MANNER_ATTN_FWD_LONG
     MANNER_LAUNCH_CHECK();
   }
@@ -817,9 +864,9 @@ int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16
 
 int attn_train_mfma_backward(DType dt, const void* qkv16, const void* dctx, bool dctx_is16, const void* ctx, bool ctx_is16, const float2* ml,
                              float* dqkv, void* dqkv16, void* dctx16, float* dsum, const int32_t* cu, int64_t n_news, int heads, int H,
-                             int max_len, Drop drop, int64_t m_bound, const int* m_total, hipStream_t stream) {
+                             int max_len, Drop drop, int64_t m_bound, const int* m_total, hipStream_t stream, const int32_t* klen) {
   int rc;
-  if ((rc = check_shape(dt, heads, H, max_len)) || (rc = ensure_lds())) return rc;
+  if ((rc = check_shape(dt, heads, H, max_len, klen)) || (rc = ensure_lds())) return rc;
   if (!dqkv && !dqkv16) return fail(MANNER_HIP_E_INVALID, "attn_train_mfma_backward: no output");
   if (dctx_is16) dctx16 = const_cast<void*>(dctx);          // d ctx arrived in the 16-bit type: it IS the operand of the two kernels
   const int64_t pairs = n_news * heads;
@@ -852,17 +899,17 @@ int attn_train_mfma_backward(DType dt, const void* qkv16, const void* dctx, bool
   if (max_len > MANNER_HIP_MAX_LEN) {                         // rows of 129 .. max_len tokens, after the pre-pass above
     const LongGrid lq = long_grid(pairs, max_len, LONG_Q_WAVES), lkv = long_grid(pairs, max_len, LONG_KV_WAVES);
     const size_t lds_lq = (size_t)lq.rows_cap * 256 + LONG_Q_WAVES * 4096, lds_lkv = (size_t)lkv.rows_cap * (256 + 12) + LONG_KV_WAVES * 4096;
-#define MANNER_ATTN_BWD_LONG(TE_)                                                                                                             \
+#define MANNER_ATTN_BWD_LONG(TE_, KEYS_)                                                                                                      \
   do {                                                                                                                                        \
-    hipLaunchKernelGGL(attn_train_mfma_bwd_q_long_kernel<TE_>, dim3(lq.grid), dim3(64 * LONG_Q_WAVES), lds_lq, stream,                         \
+    hipLaunchKernelGGL((attn_train_mfma_bwd_q_long_kernel<TE_, KEYS_>), dim3(lq.grid), dim3(64 * LONG_Q_WAVES), lds_lq, stream,                \
                        static_cast<const TE_*>(qkv16), static_cast<const TE_*>(dctx16), ml, dsum, dqkv, static_cast<TE_*>(dqkv16), cu, pairs,  \
-                       lq.n_blk, heads, H, lq.rows_cap, drop);                                                                                 \
-    hipLaunchKernelGGL(attn_train_mfma_bwd_kv_long_kernel<TE_>, dim3(lkv.grid), dim3(64 * LONG_KV_WAVES), lds_lkv, stream,                     \
+                       lq.n_blk, heads, H, lq.rows_cap, drop, klen);                                                                           \
+    hipLaunchKernelGGL((attn_train_mfma_bwd_kv_long_kernel<TE_, KEYS_>), dim3(lkv.grid), dim3(64 * LONG_KV_WAVES), lds_lkv, stream,            \
                        static_cast<const TE_*>(qkv16), static_cast<const TE_*>(dctx16), ml, dsum, dqkv, static_cast<TE_*>(dqkv16), cu, pairs,  \
-                       lkv.n_blk, heads, H, lkv.rows_cap, drop);                                                                               \
+                       lkv.n_blk, heads, H, lkv.rows_cap, drop, klen);                                                                         \
   } while (0)
-    if (dt == DT_F16) MANNER_ATTN_BWD_LONG(f16_t);
-    else MANNER_ATTN_BWD_LONG(bf16_t);
+    if (dt == DT_F16) { if (klen) MANNER_ATTN_BWD_LONG(f16_t, true); else MANNER_ATTN_BWD_LONG(f16_t, false); }
+    else { if (klen) MANNER_ATTN_BWD_LONG(bf16_t, true); else MANNER_ATTN_BWD_LONG(bf16_t, false); }
 #undef MANNER_ATTN_BWD_LONG
     MANNER_LAUNCH_CHECK();
   }

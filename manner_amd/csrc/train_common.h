@@ -77,11 +77,14 @@ int gemm_tn_gelu_grad16(DType in, const void* X, const void* W, const float* zer
 //   backward: dsum[m, heads] = dctx . ctx per head first — dctx / ctx f32 or (`*_is16`) of the type `dt`; an f32 dctx is also copied
 //             to dctx16 (scratch [m_bound, H] of `dt`), a 16-bit one is used where it lies — then d qkv [m, 3H] as f32 rows (dqkv,
 //             may be NULL) and / or 16-bit rows (dqkv16, may be NULL).  Dropout bits: attn_drop_for / attn_drop_shift.
+//   klen    : NULL, or ("full rows", max_len > MANNER_HIP_MAX_LEN only: every news then has max_len rows and runs the long-row
+//             kernels) the key count of each news, 1 <= klen[n] <= rows of the news: every row is a query, rows >= klen[n] are no
+//             keys and get d k = d v = 0 written.  With klen the forward's ml may be NULL (inference: no statistics kept).
 int attn_train_mfma_forward(DType dt, const void* qkv16, float* ctx, void* ctx16, float2* ml, const int32_t* cu, int64_t n_news,
-                            int heads, int H, int max_len, Drop drop, hipStream_t stream);
+                            int heads, int H, int max_len, Drop drop, hipStream_t stream, const int32_t* klen = nullptr);
 int attn_train_mfma_backward(DType dt, const void* qkv16, const void* dctx, bool dctx_is16, const void* ctx, bool ctx_is16, const float2* ml,
                              float* dqkv, void* dqkv16, void* dctx16, float* dsum, const int32_t* cu, int64_t n_news, int heads, int H,
-                             int max_len, Drop drop, int64_t m_bound, const int* m_total, hipStream_t stream);
+                             int max_len, Drop drop, int64_t m_bound, const int* m_total, hipStream_t stream, const int32_t* klen = nullptr);
 
 // wgrad.hip: out [slices][N, K] f32 = per-slice sums over token rows of dY[m, :]^T X[m, :] (row-major 16-bit operands read
 // transposed from LDS; slices == 1 writes dW itself); N, K % 256 == 0, rows_per_slice % 32 == 0, zero_page >= 16 zero bytes

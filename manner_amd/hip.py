@@ -681,12 +681,15 @@ def mha_axis0(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tenso
 
 def encode_full(cfg: EncoderConfig, weights: Dict[str, Tensor], ids: Tensor, mask: Tensor, precision: str = "fp32") -> Tensor:
     """HF ``last_hidden_state`` [N, Lp, H] f32 INCLUDING the padded positions (what PLMTextEncoder consumes); ``weights`` is the
-    HF-named dict of float32 GPU tensors, read in place."""
+    HF-named dict of float32 GPU tensors, read in place.  ``Lp <= _lib.MAX_LEN_FULL`` (512), every position within the model's
+    position table; in f16 / bf16 a batch of more than 128 positions runs the long-row matrix-pipe attention."""
     if precision not in ("fp32", "f16", "bf16"):
         raise ValueError("encode_full precision: fp32, f16 or bf16")
     ids, mask = _dev(ids, torch.int64, "input_ids").contiguous(), _dev(mask, torch.int64, "attention_mask").contiguous()
     if ids.dim() != 2 or ids.shape != mask.shape:
         raise ValueError(f"input_ids {tuple(ids.shape)} / attention_mask {tuple(mask.shape)} must be equal 2-D")
+    if ids.shape[1] > _lib.MAX_LEN_FULL:
+        raise RuntimeError(f"encode_full: padded_len={ids.shape[1]} (padded_len <= {_lib.MAX_LEN_FULL})")
     canon = canonical_weights(cfg, weights)
     table = [_dev(canon[n].detach(), torch.float32, n).contiguous() for n in weight_table_order(cfg)]
     n, lp = ids.shape

@@ -647,6 +647,11 @@ class PLMTextEncoder(nn.Module):
     #: MannerTextEncoder.train_precision)
     train_precision: Optional[str] = None
 
+    #: Opt-in, as MannerTextEncoder.train_max_length (same environment default): the longest padded batch train() — or eval() with a
+    #: graph — accepts.  128 keeps the short-row limit; up to 512 trains on news of 129..512 tokens.  Every padded position is a row of
+    #: the PLM here, so saved activations grow with batch x padded length.  eval() under no_grad takes up to 512 without it.
+    train_max_length: int = int(os.environ.get("MANNER_HIP_TRAIN_MAX_LEN", "128"))
+
     def forward(self, tokenized_text) -> torch.Tensor:
         ids, mask = tokenized_text["input_ids"], tokenized_text["attention_mask"]
         if not ids.is_cuda:
@@ -666,7 +671,7 @@ class PLMTextEncoder(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             x = train.encode_full_train(plm.cfg, params, ids, mask, precision=self.train_precision or autocast_mode() or "fp32",
                                         p_hidden=on * plm.hidden_dropout_prob,
-                                        p_attn=on * plm.attention_probs_dropout_prob, seed=seed)
+                                        p_attn=on * plm.attention_probs_dropout_prob, seed=seed, max_len=self.train_max_length)
             x = train.dropout(x, on * self.dropout.p, seed, site=4)
             x = train.mha_axis0(x, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias, mha.num_heads)
             x = train.dropout(x, on * self.dropout.p, seed, site=5)

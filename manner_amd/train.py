@@ -322,14 +322,24 @@ class _EncodeFullTrain(torch.autograd.Function):
 
 
 def encode_full_train(cfg: EncoderConfig, params: Dict[str, Tensor], ids: Tensor, mask: Tensor, *, precision: str = "fp32",
-                      p_hidden: float = 0.1, p_attn: float = 0.1, seed: int = 0) -> Tensor:
+                      p_hidden: float = 0.1, p_attn: float = 0.1, seed: int = 0, max_len: int = _lib.MAX_LEN) -> Tensor:
     """[N, Lp] ids / mask -> HF ``last_hidden_state`` [N, Lp, H] including the padded positions (``hip.encode_full`` with
-    autograd and HF's dropouts): what ``PLMTextEncoder`` feeds its un-masked attention in train() mode."""
+    autograd and HF's dropouts): what ``PLMTextEncoder`` feeds its un-masked attention in train() mode.
+
+    ``max_len``: the longest padded batch this call accepts, as in ``encode_train`` (``Lp > max_len`` raises ``RuntimeError``); up to
+    ``_lib.MAX_LEN_FULL`` (512) opts in to batches of 129..512 positions.  Every position is a row here, so ``saved`` grows with
+    N * Lp; every position must also fit the model's position table."""
     if precision not in _TRAIN_PRECISIONS:
         raise ValueError(f"training precision {precision!r}: one of {_TRAIN_PRECISIONS}")
+    if not 1 <= int(max_len) <= _lib.MAX_LEN_FULL:
+        raise ValueError(f"max_len={max_len}: full-row training takes padded batches of 1..{_lib.MAX_LEN_FULL} tokens")
     ids, mask = hip._dev(ids, torch.int64, "input_ids").contiguous(), hip._dev(mask, torch.int64, "attention_mask").contiguous()
     if ids.dim() != 2 or ids.shape != mask.shape:
         raise ValueError(f"input_ids {tuple(ids.shape)} / attention_mask {tuple(mask.shape)} must be equal 2-D")
+    if ids.shape[1] > int(max_len):
+        raise RuntimeError(f"train (full rows): padded_len={ids.shape[1]} beyond max_len={int(max_len)} (padded_len <= {int(max_len)}); "
+                           f"news of up to {_lib.MAX_LEN_FULL} tokens train with max_len={_lib.MAX_LEN_FULL} "
+                           f"(PLMTextEncoder.train_max_length, MANNER_HIP_TRAIN_MAX_LEN)")
     canon = canonical_weights(cfg, params)
     table = [canon[name] for name in hip.weight_table_order(cfg)]
     for name, t in zip(hip.weight_table_order(cfg), table):
