@@ -932,9 +932,18 @@ __host__ __device__ inline int panel_rows(int M, int n_tiles, int cus, int mode)
 // (mt, nt): shared by the 8-wave kernel (ew = its wave: column group ew & 3, row half ew >> 2) and by the 4-wave kernel (round 6), whose
 // waves own 128 x 128 and call it once per 64-column half with the virtual wave index 4 wm + 2 wn + half — the same expressions in the
 // same order, hence the same bits.  slab / rslab1: two wave-private 4 KiB LDS slabs (rslab1: EPI_NRES only; ONE_SLAB: it has one).
-template <typename TE, typename TOut, int EPI, int ABL, int MBT, bool ONE_SLAB = false>
+// PRE (gemm_tn_w8_kernel only): the tile's constants — bias, dln.vec, its rows' {mean, rstd} — already lie in `slab` (w8_prefetch_consts
+// put them there ahead of the K-loop: EPC_BIAS / EPC_VEC / EPC_MR) and are read from it instead of from memory: the same values into
+// the same registers.  They are all read before the first write to the slab (a wave's LDS operations execute in program order).
+constexpr int EPC_BIAS = 0, EPC_VEC = 256, EPC_MR = 512;     // 64 floats | 64 floats | 128 rows of float2
+template <typename TE, typename TOut, int EPI, int ABL, int MBT, bool ONE_SLAB = false, bool PRE = false>
 __device__ __forceinline__ void x16_epilogue(f32x4 (&acc)[4][MBT], char* slab, char* rslab1, int lane, int ew, int mt, int nt, int M, int N,
-                                             const float* __restrict__ bias, const TE* __restrict__ R, TOut* __restrict__ Y, const DlnAux& dln) {
+                                             const float* __restrict__ bias, const TE* __restrict__ R, TOut* __restrict__ Y, const DlnAux& dln
+#ifdef MANNER_W8_STAMPS   // lab build only: the shader clock once the constants are in registers (the end of the epilogue's "open")
+                                             , uint64_t* open_stamp = nullptr
+#endif
+) {
+  static_assert(!PRE || (ONE_SLAB && MBT == 8), "the slab holds the constants of a 128-row wave block");
   typedef typename E16<TE>::v8 e16x8;
   typedef typename E16<TE>::v4 e16x4;
   constexpr int TM = 32 * MBT, WROWS = TM / 2;
@@ -960,11 +969,35 @@ __device__ __forceinline__ void x16_epilogue(f32x4 (&acc)[4][MBT], char* slab, c
         for (int bb = 0; bb < MBT; ++bb) asm volatile("" ::"v"(acc[a][bb]));
     } else {
       f32x4 bv[4], g4[4];
+      float2 ms_pre[PRE ? MBT : 1];                    // PRE: both halves' rows, read before half 0's residual overwrites the slab
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        bv[a] = *reinterpret_cast<const f32x4*>(bias + nbase + 16 * a + 4 * lq);
-        g4[a] = *reinterpret_cast<const f32x4*>(dln.vec + nbase + 16 * a + 4 * lq);
+        if constexpr (PRE) {
+          bv[a] = *reinterpret_cast<const f32x4*>(slab + EPC_BIAS + 64 * a + 16 * lq);
+          g4[a] = *reinterpret_cast<const f32x4*>(slab + EPC_VEC + 64 * a + 16 * lq);
+        } else {
+          bv[a] = *reinterpret_cast<const f32x4*>(bias + nbase + 16 * a + 4 * lq);
+          g4[a] = *reinterpret_cast<const f32x4*>(dln.vec + nbase + 16 * a + 4 * lq);
+        }
       }
+      if constexpr (PRE) {
+#pragma unroll
+        for (int bb = 0; bb < MBT; ++bb) ms_pre[bb] = *reinterpret_cast<const float2*>(slab + EPC_MR + 8 * (16 * bb + l15));
+      }
+#ifdef MANNER_W8_STAMPS
+      if (open_stamp) {
+        if constexpr (!PRE) {                          // (this path asks for its rows per half: the first half's are the open)
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) { float2 t_ = dln.mr[min(mrow0 + 16 * bb + l15, M - 1)]; asm volatile("" ::"v"(t_)); }
+        } else {
+#pragma unroll
+          for (int bb = 0; bb < MBT; ++bb) asm volatile("" : "+v"(ms_pre[bb]));
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) asm volatile("" : "+v"(bv[a]), "+v"(g4[a]));
+        *open_stamp = __builtin_amdgcn_s_memtime();
+      }
+#endif
       // The residual is fetched as whole 128-byte row segments (16 B per lane, the same coalesced shape as the
       // output stores) and turned into the MFMA layout through two wave-private 4 KiB LDS slabs: 8-byte loads
       // straight in the MFMA layout touch 16 rows per instruction and cost ~10 us per tile in the address path.
@@ -985,7 +1018,10 @@ __device__ __forceinline__ void x16_epilogue(f32x4 (&acc)[4][MBT], char* slab, c
             rawres[sb][q] = ABL == 3 ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(R + (size_t)m * N + nbase + 8 * (rsl ^ (row & 7)));
           }
 #pragma unroll
-        for (int b4 = 0; b4 < nb4; ++b4) ms[b4] = dln.mr[min(mrow0 + 16 * (4 * hb + b4) + l15, M - 1)];
+        for (int b4 = 0; b4 < nb4; ++b4) {
+          if constexpr (PRE) ms[b4] = ms_pre[4 * hb + b4];
+          else ms[b4] = dln.mr[min(mrow0 + 16 * (4 * hb + b4) + l15, M - 1)];
+        }
         e16x4 res[4][4];
         if constexpr (!ONE_SLAB) {                     // two slabs: both 32-row sub-blocks go through LDS at once
 #pragma unroll
@@ -1094,7 +1130,10 @@ __device__ __forceinline__ void x16_epilogue(f32x4 (&acc)[4][MBT], char* slab, c
   const int row0 = el / CHUNKS, sl = el % CHUNKS;
   f32x4 bv[4];
 #pragma unroll
-  for (int a = 0; a < 4; ++a) bv[a] = *reinterpret_cast<const f32x4*>(bias + nbase + 16 * a + 4 * lq);
+  for (int a = 0; a < 4; ++a) {
+    if constexpr (PRE) bv[a] = *reinterpret_cast<const f32x4*>(slab + EPC_BIAS + 64 * a + 16 * lq);
+    else bv[a] = *reinterpret_cast<const f32x4*>(bias + nbase + 16 * a + 4 * lq);
+  }
   constexpr bool NORM = EPI == EPI_NORM || EPI == EPI_NORM_GELU;   // deferred LayerNorm of the A operand
   constexpr bool SPLIT = EPI == EPI_BIAS_GELU_SPLIT3;              // 16-bit [hi | hi | lo] output rows of 3 N elements
   const size_t ldy = SPLIT ? (size_t)3 * N : (size_t)N;
@@ -1103,10 +1142,29 @@ __device__ __forceinline__ void x16_epilogue(f32x4 (&acc)[4][MBT], char* slab, c
   const int mrow0 = mt * TM + wm * WROWS;            // first row of this wave's tile
   if constexpr (NORM) {
 #pragma unroll
-    for (int a = 0; a < 4; ++a) cv[a] = *reinterpret_cast<const f32x4*>(dln.vec + nbase + 16 * a + 4 * lq);
+    for (int a = 0; a < 4; ++a) {
+      if constexpr (PRE) cv[a] = *reinterpret_cast<const f32x4*>(slab + EPC_VEC + 64 * a + 16 * lq);
+      else cv[a] = *reinterpret_cast<const f32x4*>(dln.vec + nbase + 16 * a + 4 * lq);
+    }
 #pragma unroll
-    for (int bb = 0; bb < MBT; ++bb) ms[bb] = dln.mr[min(mrow0 + 16 * bb + l15, M - 1)];
+    for (int bb = 0; bb < MBT; ++bb) {
+      if constexpr (PRE) ms[bb] = *reinterpret_cast<const float2*>(slab + EPC_MR + 8 * (16 * bb + l15));
+      else ms[bb] = dln.mr[min(mrow0 + 16 * bb + l15, M - 1)];
+    }
   }
+#ifdef MANNER_W8_STAMPS
+  if (open_stamp) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) asm volatile("" : "+v"(bv[a]));
+    if constexpr (NORM) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) asm volatile("" : "+v"(cv[a]));
+#pragma unroll
+      for (int bb = 0; bb < MBT; ++bb) asm volatile("" : "+v"(ms[bb]));
+    }
+    *open_stamp = __builtin_amdgcn_s_memtime();
+  }
+#endif
   constexpr int SLAB_ROWS = 4096 / OUT_ROW;          // 32 tokens (bf16) / 16 tokens (f32) per slab
   constexpr int MB = SLAB_ROWS / 16;                 // MFMA token blocks per slab
   constexpr int SQ = SLAB_ROWS / ROWS_PER_INST;      // row-contiguous 16-byte instructions per slab (4)
@@ -1615,7 +1673,50 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_x16_kernel(
 // (staged by the previous tile's last steps / by the prologue here); 2 stages x [W 32 KiB | X 32 KiB] at 0 and 64 KiB (the stage is
 // bit 16 of an LDS address), one 4 KiB epilogue slab per wave at 128 KiB.  256-row panels only (the host launches this kernel where
 // panel_rows() picks 256; 192-row launches keep the LDS-DMA kernel).
-template <typename TE, typename TOut, int EPI, int ABL = 0>
+//
+// PRE (MANNER_HIP_EPI_PREFETCH, docs/rounds/r7.md): the epilogue's constants are staged into the wave's slab under the K-loop.
+// x16_epilogue opens with global loads whose values it needs at once, and vector-memory loads return in order: those loads came
+// back behind the next tile's operand requests, which the K-loop's last steps had just issued.  With PRE every wave requests, at
+// the top of the tile loop, what its own epilogue reads — bias[64], dln.vec[64], dln.mr[128 rows] — by LDS-DMA (no register lives
+// across the K-loop) into the slab, which is idle until the epilogue; the epilogue then opens with ds_reads.
+//   - the slab is free: the previous tile's epilogue has issued its last row stores, whose data its last ds_reads of the slab
+//     delivered, and the statement's "memory" clobber keeps it behind them;
+//   - the counted waits of the K-loop still hold: the prefetch is OLDER than every load of the K-loop, so "at most n loads
+//     outstanding" covers what it covered before (tools/gen_gemm_w.py counts the loads YOUNGER than the one a wait is for; an older
+//     load can only make a wait conservative, and the previous epilogue's stores were already in that position);
+//   - it has landed before the epilogue: every tile has >= 3 K-steps, and from the second on each piece's wait (vmcnt(NP - 1) or
+//     less) retires everything older than the step before's requests — the epilogue needs no vector-memory wait of its own, and the
+//     compiler, which does not see the DMA, inserts none (the next tile's LDS-DMA pieces stay in flight through the epilogue);
+//   - M0 is set inside the statement and put back; nothing is assumed of it afterwards.
+template <int EPI>
+__device__ __forceinline__ void w8_prefetch_consts(uint32_t slab_lds, int lane, int nbase, int mrow0, int M, const float* bias, const DlnAux& dln) {
+  constexpr bool ROWS = EPI == EPI_NORM || EPI == EPI_NORM_GELU || EPI == EPI_NRES;
+  int keep;
+  const uint32_t ob = (uint32_t)(nbase + lane) * 4u;   // one float per lane: 256 B per instruction, lane l -> slab + 4 l
+  // (s_nop 4: the base pair may come fresh from scalar arithmetic; s_nop 0: M0 written by the SALU, read by the DMA)
+  asm volatile("s_nop 4\n\ts_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[dst]\n\ts_nop 0\n\tglobal_load_lds_dword %[ob], %[src]\n\ts_mov_b32 m0, %[keep]"
+               : [keep] "=&s"(keep) : [dst] "s"(slab_lds + EPC_BIAS), [ob] "v"(ob), [src] "s"(bias) : "memory");
+  if constexpr (ROWS) {
+    // {mean, rstd} of the wave's 128 rows, half a row per lane (4 x 32 rows), clamped to the last row as the epilogue's own loads are
+    uint32_t om[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) om[j] = (uint32_t)min(mrow0 + 32 * j + (lane >> 1), M - 1) * 8u + (uint32_t)(lane & 1) * 4u;
+    asm volatile("s_nop 4\n\ts_mov_b32 %[keep], m0\n\t"
+                 "s_mov_b32 m0, %[dv]\n\ts_nop 0\n\tglobal_load_lds_dword %[ob], %[vec]\n\t"
+                 "s_mov_b32 m0, %[d0]\n\ts_nop 0\n\tglobal_load_lds_dword %[o0], %[mr]\n\t"
+                 "s_mov_b32 m0, %[d1]\n\ts_nop 0\n\tglobal_load_lds_dword %[o1], %[mr]\n\t"
+                 "s_mov_b32 m0, %[d2]\n\ts_nop 0\n\tglobal_load_lds_dword %[o2], %[mr]\n\t"
+                 "s_mov_b32 m0, %[d3]\n\ts_nop 0\n\tglobal_load_lds_dword %[o3], %[mr]\n\t"
+                 "s_mov_b32 m0, %[keep]"
+                 : [keep] "=&s"(keep)
+                 : [dv] "s"(slab_lds + EPC_VEC), [d0] "s"(slab_lds + EPC_MR), [d1] "s"(slab_lds + EPC_MR + 256), [d2] "s"(slab_lds + EPC_MR + 512),
+                   [d3] "s"(slab_lds + EPC_MR + 768), [ob] "v"(ob), [o0] "v"(om[0]), [o1] "v"(om[1]), [o2] "v"(om[2]), [o3] "v"(om[3]),
+                   [vec] "s"(dln.vec), [mr] "s"(dln.mr)
+                 : "memory");
+  }
+}
+
+template <typename TE, typename TOut, int EPI, int ABL = 0, bool PRE = false>
 __global__ __launch_bounds__(512, 1) void gemm_tn_w8_kernel(
     const TE* __restrict__ X, const TE* __restrict__ W, const float* __restrict__ bias,
     const TE* __restrict__ R, TOut* __restrict__ Y, int N, int K, const int* __restrict__ m_total,
@@ -1702,12 +1803,16 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_w8_kernel(
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
 #ifdef MANNER_W8_STAMPS
-  uint64_t stamp_k = 0, stamp_e = 0, stamp_n = 0;
+  uint64_t stamp_k = 0, stamp_e = 0, stamp_n = 0, stamp_o = 0;
 #endif
   char* slab = lds + 4 * G_OP_BYTES + wave * 4096;     // one wave-private 4 KiB epilogue slab in the 32 KiB behind the stages
+  static_assert(!PRE || (ABL == 0 && sizeof(TOut) == 2 && (EPI == EPI_BIAS || EPI == EPI_NORM || EPI == EPI_NORM_GELU || EPI == EPI_NRES)),
+                "the epilogue classes of the 16-bit encoder layer");
+  const uint32_t slab_lds = __builtin_amdgcn_readfirstlane(lds0 + 4 * G_OP_BYTES + wave * 4096);
   while (true) {
     int mt, nt;
     decode(t, mt, nt);
+    if constexpr (PRE) w8_prefetch_consts<EPI>(slab_lds, lane, nt * G_BN + wn * 64, mt * G_BM + wm * 128, M, bias, dln);
     const int tn = t + walk.stride;
     const bool has_next = tn < walk.end;
     // (readfirstlane: the asm block takes them as SGPR pairs — "s" — and the compiler must not doubt that they are wave-uniform)
@@ -1771,7 +1876,13 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_w8_kernel(
         }
       int ew = wave;
       asm volatile("" : "+s"(ew));
-      x16_epilogue<TE, TOut, EPI, ABL, 8, true>(acc, slab, slab, lane, ew, mt, nt, M, N, bias, R, Y, dln);
+#ifdef MANNER_W8_STAMPS
+      uint64_t sto = st1;
+      x16_epilogue<TE, TOut, EPI, ABL, 8, true, PRE>(acc, slab, slab, lane, ew, mt, nt, M, N, bias, R, Y, dln, ABL == 0 ? &sto : nullptr);
+      stamp_o += sto - st1;
+#else
+      x16_epilogue<TE, TOut, EPI, ABL, 8, true, PRE>(acc, slab, slab, lane, ew, mt, nt, M, N, bias, R, Y, dln);
+#endif
     }
     if constexpr (EPI == EPI_NRES && ABL == 0)
       if (dln.fin_mr) nres_fan_in<G_BM>(dln, mt, M, n_tiles, wave, lane);
@@ -1785,9 +1896,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_w8_kernel(
     t = tn;
   }
 #ifdef MANNER_W8_STAMPS
-  if (lane == 0 && dln.aux32) {                        // {cycles in K-loops, cycles in epilogues, tiles} per wave
-    uint64_t* dst = reinterpret_cast<uint64_t*>(const_cast<float*>(dln.aux32)) + ((size_t)blk * 8 + wave) * 3;
-    dst[0] = stamp_k; dst[1] = stamp_e; dst[2] = stamp_n;
+  if (lane == 0 && dln.aux32) {                        // {cycles in K-loops, in epilogues, tiles, in the epilogues' opens} per wave
+    uint64_t* dst = reinterpret_cast<uint64_t*>(const_cast<float*>(dln.aux32)) + ((size_t)blk * 8 + wave) * 4;
+    dst[0] = stamp_k; dst[1] = stamp_e; dst[2] = stamp_n; dst[3] = stamp_o;
   }
 #endif
 }
@@ -2113,6 +2224,13 @@ static int pick_col_group(int64_t m_est, int N, int K, int cus) {
   return (groups - 1) * x_bytes < 8.0 * (double)(rounds - 1) * w_bytes ? (n_tiles + groups - 1) / groups : 0;
 }
 
+// MANNER_HIP_EPI_PREFETCH (read per launch: the equality tests flip it): 1 = gemm_tn_w8_kernel stages each tile's epilogue constants in
+// the wave's LDS slab under the K-loop (its PRE instantiation), 0 = the epilogue opens with global loads.  The same bits either way.
+static bool epi_prefetch() {
+  const char* e = getenv("MANNER_HIP_EPI_PREFETCH");
+  return e ? atoi(e) != 0 : true;
+}
+
 // The tile order of a persistent launch from the two switches (read per launch: the equality tests flip them)
 static void set_tile_order(DlnAux& aux, int64_t m_est, int N, int K) {
   const char* cg_env = getenv("MANNER_HIP_COL_GROUP");
@@ -2142,6 +2260,12 @@ int launch_x16(Epilogue epi, const void* X, const void* W, const float* bias, co
     g = dim3((unsigned)(tiles < cus ? tiles : cus));
     switch (epi) {
       case EPI_BIAS:
+        if constexpr (sizeof(TOut) == 2) {
+          if (epi_prefetch()) {
+            hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TOut, EPI_BIAS, 0, true>), g, b, 0, stream, x, w, bias, r, y, N, K, m_total, n_tiles, aux0);
+            break;
+          }
+        }
         hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TOut, EPI_BIAS>), g, b, 0, stream, x, w, bias, r, y, N, K, m_total, n_tiles, aux0);
         break;
       case EPI_BIAS_GELU:
@@ -2265,15 +2389,19 @@ static int launch_dln(Epilogue epi, const void* X, const void* W, const float* b
   const TE* w = static_cast<const TE*>(W);
   TE* y = static_cast<TE*>(Y);
   if (asm_mode == 8) {                                 // round 6: the hand-scheduled 8-wave kernel (same bits; 256-row panels)
+    const bool pre = epi_prefetch();                   // a second instantiation, not a branch inside the kernel
     switch (epi) {
       case EPI_NORM:
-        hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NORM>), g, b, 0, stream, x, w, bias, nullptr, y, N, K, m_total, n_tiles, aux);
+        if (pre) hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NORM, 0, true>), g, b, 0, stream, x, w, bias, nullptr, y, N, K, m_total, n_tiles, aux);
+        else hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NORM>), g, b, 0, stream, x, w, bias, nullptr, y, N, K, m_total, n_tiles, aux);
         break;
       case EPI_NORM_GELU:
-        hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NORM_GELU>), g, b, 0, stream, x, w, bias, nullptr, y, N, K, m_total, n_tiles, aux);
+        if (pre) hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NORM_GELU, 0, true>), g, b, 0, stream, x, w, bias, nullptr, y, N, K, m_total, n_tiles, aux);
+        else hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NORM_GELU>), g, b, 0, stream, x, w, bias, nullptr, y, N, K, m_total, n_tiles, aux);
         break;
       case EPI_NRES:
-        hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NRES>), g, b, 0, stream, x, w, bias, y, y, N, K, m_total, n_tiles, aux);
+        if (pre) hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NRES, 0, true>), g, b, 0, stream, x, w, bias, y, y, N, K, m_total, n_tiles, aux);
+        else hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI_NRES>), g, b, 0, stream, x, w, bias, y, y, N, K, m_total, n_tiles, aux);
         break;
       default:
         return fail(MANNER_HIP_E_INVALID, "gemm_dln: epilogue %d", (int)epi);

@@ -307,6 +307,81 @@ struct AsmKernel {
   }
 };
 
+// 'stamps': in-kernel shader-clock split of the integrated kernels, per tile and wave: the K-loop, the whole epilogue and its OPEN (up
+// to the point where bias, dln.vec and the rows' {mean, rstd} are in registers).  w8 rows: every epilogue class of the encoder layer
+// with the constants fetched by the epilogue (pre 0) and staged in the slab under the K-loop (pre 1), bf16 and f16; NRES (in place,
+// no fan-in) on the N = 768 shapes it runs at.  x16 rows: the compiler-scheduled kernel, bf16, as before.
+template <typename TE, int EPI, bool PRE>
+static void stamps_w8(const char* shape, const char* dt, const char* epi, dim3 g, const TE* X, const TE* W, const float* bias, TE* Y, int N, int K,
+                      const int* mtot, int n_tiles, const DlnAux& ax, uint64_t* st) {
+  CK(hipMemset(st, 0, 256 * 8 * 4 * 8));
+  if (EPI == EPI_NRES) CK(hipMemset(Y, 0, (size_t)ax.part_stride * N * 2));   // (in place: Y is its own residual; part_stride = M here)
+  hipLaunchKernelGGL((gemm_tn_w8_kernel<TE, TE, EPI, 0, PRE>), g, dim3(512), 0, 0, X, W, bias, EPI == EPI_NRES ? (const TE*)Y : (const TE*)nullptr, Y, N, K, mtot, n_tiles, ax);
+  CK(hipDeviceSynchronize());
+  std::vector<uint64_t> h(256 * 8 * 4);
+  CK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+  double sk = 0, se = 0, sn = 0, so = 0;
+  for (size_t i = 0; i < h.size(); i += 4) { sk += h[i]; se += h[i + 1]; sn += h[i + 2]; so += h[i + 3]; }
+  printf("stamps %-4s w8  %-4s %-9s pre %d: per tile and wave: K-loop %.0f cycles, epilogue %.0f cycles, of which open %.0f (shader clock), %.0f tiles x waves\n",
+         shape, dt, epi, (int)PRE, sk / sn, se / sn, so / sn, sn);
+}
+
+template <typename TE>
+static void stamps_dtype(const char* shape, const char* dt, dim3 g, const TE* X, const TE* W, const float* bias, TE* Y, int N, int K, const int* mtot,
+                         int n_tiles, const DlnAux& ax, uint64_t* st) {
+  stamps_w8<TE, EPI_BIAS, false>(shape, dt, "BIAS", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  stamps_w8<TE, EPI_BIAS, true>(shape, dt, "BIAS", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  stamps_w8<TE, EPI_NORM, false>(shape, dt, "NORM", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  stamps_w8<TE, EPI_NORM, true>(shape, dt, "NORM", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  stamps_w8<TE, EPI_NORM_GELU, false>(shape, dt, "NORM_GELU", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  stamps_w8<TE, EPI_NORM_GELU, true>(shape, dt, "NORM_GELU", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  if (N == 768) {
+    stamps_w8<TE, EPI_NRES, false>(shape, dt, "NRES", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+    stamps_w8<TE, EPI_NRES, true>(shape, dt, "NRES", g, X, W, bias, Y, N, K, mtot, n_tiles, ax, st);
+  }
+}
+
+static void stamps_rows(const char* shape, int N, int K, int M, const bf16_t* X, const bf16_t* W, const std::vector<bf16_t>& hx,
+                        const std::vector<bf16_t>& hw, const float* bias, bf16_t* Y16, const int* mtot, const DlnAux& aux) {
+  const int n_tiles = N / 256, tiles = (M / 256) * n_tiles;
+  dim3 g(tiles < 256 ? tiles : 256);
+  uint64_t* st; CK(hipMalloc(&st, 256 * 8 * 4 * 8));
+  DlnAux ax = aux; ax.aux32 = reinterpret_cast<const float*>(st);
+  std::vector<float2> hm(M, float2{0.01f, 1.0f});
+  float2 *mr, *part; float* vec;
+  CK(hipMalloc(&mr, (size_t)M * 8)); CK(hipMalloc(&vec, 3072 * 4)); CK(hipMalloc(&part, (size_t)M * 8 * 12));
+  CK(hipMemcpy(mr, hm.data(), (size_t)M * 8, hipMemcpyHostToDevice));
+  std::vector<float> hv(3072, 1.0f); CK(hipMemcpy(vec, hv.data(), 3072 * 4, hipMemcpyHostToDevice));
+  ax.vec = vec; ax.mr = mr; ax.part = part; ax.part_stride = M;
+  stamps_dtype<bf16_t>(shape, "bf16", g, X, W, bias, Y16, N, K, mtot, n_tiles, ax, st);
+  {                                                      // the same values as f16 operands
+    static f16_t *Xh = nullptr, *Wh = nullptr;
+    if (!Xh) {
+      std::vector<f16_t> t(hx.size());
+      for (size_t i = 0; i < hx.size(); ++i) t[i] = (f16_t)(float)hx[i];
+      CK(hipMalloc(&Xh, t.size() * 2)); CK(hipMemcpy(Xh, t.data(), t.size() * 2, hipMemcpyHostToDevice));
+      t.resize(hw.size());
+      for (size_t i = 0; i < hw.size(); ++i) t[i] = (f16_t)(float)hw[i];
+      CK(hipMalloc(&Wh, t.size() * 2)); CK(hipMemcpy(Wh, t.data(), t.size() * 2, hipMemcpyHostToDevice));
+    }
+    stamps_dtype<f16_t>(shape, "f16", g, Xh, Wh, bias, reinterpret_cast<f16_t*>(Y16), N, K, mtot, n_tiles, ax, st);
+  }
+  for (int e = 0; e < 3; ++e) {
+    CK(hipMemset(st, 0, 256 * 8 * 3 * 8));
+    if (e == 0) hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_BIAS, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, N, K, mtot, n_tiles, ax);
+    else if (e == 1) hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_NORM, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, N, K, mtot, n_tiles, ax);
+    else hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_NORM_GELU, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, N, K, mtot, n_tiles, ax);
+    CK(hipDeviceSynchronize());
+    std::vector<uint64_t> h(256 * 8 * 3);
+    CK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+    double sk = 0, se = 0, sn = 0;
+    for (size_t i = 0; i < h.size(); i += 3) { sk += h[i]; se += h[i + 1]; sn += h[i + 2]; }
+    printf("stamps %-4s x16 bf16 %-9s      : per tile and wave: K-loop %.0f cycles, epilogue %.0f cycles (shader clock), %.0f tiles x waves\n", shape,
+           e == 0 ? "BIAS" : e == 1 ? "NORM" : "NORM_GELU", sk / sn, se / sn, sn);
+  }
+  CK(hipFree(st)); CK(hipFree(mr)); CK(hipFree(vec)); CK(hipFree(part));
+}
+
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 65536;
   const bool check = argc > 2 && !strcmp(argv[2], "check");
@@ -420,32 +495,7 @@ int main(int argc, char** argv) {
         tw8f = time_us([&] { hipLaunchKernelGGL((gemm_tn_w8_kernel<bf16_t, bf16_t, EPI_BIAS, 0>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, aux); }, iters);
       if (want("prodfull"))
         tpf = time_us([&] { hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_BIAS, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, aux); }, iters);
-      if (want("stamps")) {                              // in-kernel shader-clock split of the integrated kernel: K-loops vs epilogues, per tile
-        uint64_t* st; CK(hipMalloc(&st, 256 * 8 * 3 * 8)); CK(hipMemset(st, 0, 256 * 8 * 3 * 8));
-        DlnAux ax = aux; ax.aux32 = reinterpret_cast<const float*>(st);
-        std::vector<float2> hm(M, float2{0.01f, 1.0f});
-        float2* mr; float* vec; CK(hipMalloc(&mr, (size_t)M * 8)); CK(hipMalloc(&vec, 3072 * 4));
-        CK(hipMemcpy(mr, hm.data(), (size_t)M * 8, hipMemcpyHostToDevice));
-        std::vector<float> hv(3072, 1.0f); CK(hipMemcpy(vec, hv.data(), 3072 * 4, hipMemcpyHostToDevice));
-        ax.vec = vec; ax.mr = mr; ax.part_stride = M;
-        for (int e = 0; e < 6; ++e) {
-          CK(hipMemset(st, 0, 256 * 8 * 3 * 8));
-          if (e == 3) hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_BIAS, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, ax);
-          else if (e == 4) hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_NORM, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, ax);
-          else if (e == 5) hipLaunchKernelGGL((gemm_tn_x16_kernel<bf16_t, bf16_t, EPI_NORM_GELU, 0, false>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, ax);
-          else if (e == 0) hipLaunchKernelGGL((gemm_tn_w8_kernel<bf16_t, bf16_t, EPI_BIAS, 0>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, ax);
-          else if (e == 1) hipLaunchKernelGGL((gemm_tn_w8_kernel<bf16_t, bf16_t, EPI_NORM, 0>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, ax);
-          else hipLaunchKernelGGL((gemm_tn_w8_kernel<bf16_t, bf16_t, EPI_NORM_GELU, 0>), g, dim3(512), 0, 0, X, W, bias, (const bf16_t*)nullptr, Y16, s.N, s.K, mtot, n_tiles, ax);
-          CK(hipDeviceSynchronize());
-          std::vector<uint64_t> h(256 * 8 * 3);
-          CK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
-          double sk = 0, se = 0, sn = 0;
-          for (size_t i = 0; i < h.size(); i += 3) { sk += h[i]; se += h[i + 1]; sn += h[i + 2]; }
-          printf("stamps %-4s %s %-9s: per tile and wave: K-loop %.0f cycles, epilogue %.0f cycles (shader clock), %.0f tiles x waves\n", s.name, e < 3 ? "w8 " : "x16",
-                 e % 3 == 0 ? "BIAS" : e % 3 == 1 ? "NORM" : "NORM_GELU", sk / sn, se / sn, sn);
-        }
-        CK(hipFree(st)); CK(hipFree(mr)); CK(hipFree(vec));
-      }
+      if (want("stamps")) stamps_rows(s.name, s.N, s.K, M, X, W, hx, hw, bias, Y16, mtot, aux);
       if (hipcc_vars && want("v0"))
         t0 = time_us([&] { hipLaunchKernelGGL((lab4::gemm4w_kernel<bf16_t, 0, false>), g, dim3(256), 0, 0, X, W, Y, s.N, s.K, M, n_tiles); }, 20);
       if (hipcc_vars && want("v1"))
