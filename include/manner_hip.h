@@ -388,6 +388,46 @@ int manner_hip_collate_aspects(const int32_t* category, const int32_t* sentiment
                                int64_t n_news, const int32_t* rows, int64_t M, int64_t* out_category,
                                int64_t* out_sentiment, float* out_score, manner_hip_stream_t stream);
 
+/* ---------------------------------------------------------------- training batches: negative sampling on the device
+ * Replaces MINDRecDatasetTrain.__getitem__ / _sample_candidates — manner/data/components/mind_rec_dataset.py:13-77
+ * (np.random.choice + np.random.permutation per impression, DataFrame.loc, pd.concat) — in front of the collate_* kernels.
+ * The data set lives on the device as the CSR arrays of the behaviours: cand_rows int32 [total], labels f32 [total],
+ * cand_off int64 [n_imp + 1] (history: hist_rows / hist_off alike), users int64 [n_imp].
+ *
+ * The sampling rule.  Positions 0..n-1 of an impression, P = positions with label == 1 (p of them), N = positions with
+ * label == 0 (q of them; any other label is in neither set), m = ratio * p.  With 64-bit wrap-around arithmetic,
+ *   mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *   key(stream, slot) = mix(mix(mix(seed + 0x9E3779B97F4A7C15 * (epoch + 1)) ^ imp) ^ (stream << 32 | slot))
+ * where imp is the impression's index in the data set — so a sample depends on (seed, epoch, imp) only, never on the
+ * batch, the place in it or the launch:
+ *   m <= q: S = the m negatives with the smallest (key(0, position), position), in that order (without replacement);
+ *   m >  q: draw t = 0..m-1 is the r-th negative in position order, r = ((key(1, t) >> 32) * q) >> 32 (with replacement);
+ *   the list [P in position order, then S] is written in ascending order of (key(2, s), s), s = the element's place in it.
+ *
+ *   sample_candidates: one workgroup per batch impression b (imp_idx int64 [B], any order, repeats allowed) writes its
+ *                      p * (1 + ratio) elements to out_rows / out_labels [out_off[b], out_off[b+1]) — out_off int64 [B + 1] is the
+ *                      host's prefix sum, out_total = out_off[B] the length of the outputs.  out_pos (int32, may be NULL) receives
+ *                      the chosen positions; users / out_users (int64 [n_imp] / [B], both or neither NULL) gather the impressions'
+ *                      user indices in the same launch.  An imp_idx outside [0, n_imp) raises MANNER_HIP_STATUS_INDEX in *status; an
+ *                      out_off segment that is not p * (1 + ratio) long or leaves [0, out_total], and p > 0 with q == 0 (where
+ *                      np.random.choice raises), raise MANNER_HIP_STATUS_LENGTHS; such an impression writes nothing.
+ *   gather_segments  : out[out_off[b] + k] = src[src_off[imp_idx[b]] + k] (src int32 [src_total], src_off int64 [n_seg + 1]); the f32
+ *                      companion src_f / out_f is gathered alike (both NULL: none).  Flags as above (a segment whose length differs
+ *                      from out_off's raises MANNER_HIP_STATUS_LENGTHS); a flagged element is written as 0.
+ *   rows_max_len     : out_max[0] = max store_len[rows[r]], out_max[1] = max store_cnt[rows[r]] (0 for store_cnt == NULL or M == 0):
+ *                      the padding=True widths of a sampled batch, for a caller that wants them exact.
+ * status (device int32) may be NULL. */
+int manner_hip_sample_candidates(const int32_t* cand_rows, const float* labels, const int64_t* cand_off, int64_t n_imp,
+                                 int64_t total, const int64_t* users, const int64_t* imp_idx, int64_t B, const int64_t* out_off,
+                                 int64_t out_total, int32_t ratio, uint64_t seed, uint64_t epoch, int32_t* out_rows,
+                                 float* out_labels, int32_t* out_pos, int64_t* out_users, int32_t* status,
+                                 manner_hip_stream_t stream);
+int manner_hip_gather_segments(const int32_t* src, const float* src_f, const int64_t* src_off, int64_t n_seg, int64_t src_total,
+                               const int64_t* imp_idx, int64_t B, const int64_t* out_off, int64_t out_total, int32_t* out,
+                               float* out_f, int32_t* status, manner_hip_stream_t stream);
+int manner_hip_rows_max_len(const int32_t* store_len, const int32_t* store_cnt, int64_t n_news, const int32_t* rows, int64_t M,
+                            int32_t* out_max, manner_hip_stream_t stream);
+
 /* ---------------------------------------------------------------- evaluation loss (val/loss, test/loss)
  * Replaces the loss of CRModule.model_step — manner/models/cr_module.py:140-171, run by validation_step and test_step
  * (:211-262) on every batch — per impression, on the ragged scores (no dense [B, Cmax] matrix, no host loops).

@@ -115,6 +115,10 @@ SIGNATURES = {
     "manner_hip_collate_text": (C.c_int, [_P, _P, _I64, _I32, _P, _I64, _I32, _I32, _P, _P, _P]),
     "manner_hip_collate_entities": (C.c_int, [_P, _P, _I64, _I32, _P, _I64, _I32, _P, _P]),
     "manner_hip_collate_aspects": (C.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "manner_hip_sample_candidates": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _I32, C.c_uint64, C.c_uint64, _P, _P, _P,
+                                               _P, _P, _P]),
+    "manner_hip_gather_segments": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "manner_hip_rows_max_len": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P]),
 }
 
 _lib = None

@@ -37,8 +37,8 @@ def _ptr(t: Optional[Tensor]) -> C.c_void_p:
 # ------------------------------------------------------------------ device-side input validation
 _STATUS_TEXT = {_lib.STATUS_MASK: "attention_mask is not a right-padded 0/1 prefix mask",
                 _lib.STATUS_TOKEN: "input id / position outside the embedding tables",
-                _lib.STATUS_INDEX: "news or entity index outside the table (IndexError in the reference)",
-                _lib.STATUS_LENGTHS: "host_lengths disagree with attention_mask"}
+                _lib.STATUS_INDEX: "news, entity or impression index outside the table (IndexError in the reference)",
+                _lib.STATUS_LENGTHS: "host_lengths disagree with attention_mask, or a batch's offsets with the data set"}
 
 
 def _status_message(flag: int) -> str:
@@ -1013,6 +1013,79 @@ def collate_aspects(category: Tensor, sentiment: Tensor, sentiment_score: Tensor
                                                           category.numel(), _ptr(rows), m, _ptr(ocat), _ptr(osent), _ptr(oscore),
                                                           _stream()))
     return ocat, osent, oscore
+
+
+# ---------------------------------------------------------------- training batches: negative sampling on the device
+def sample_candidates(cand_rows: Tensor, labels: Tensor, cand_off: Tensor, imp_idx: Tensor, out_off: Tensor, out_total: int,
+                      ratio: int, seed: int, epoch: int, users: Optional[Tensor] = None, return_pos: bool = False):
+    """The training candidates of the impressions ``imp_idx`` (int64 [B], any order, repeats allowed) of a data set held as CSR
+    arrays (``cand_rows`` int32 / ``labels`` f32 [total], ``cand_off`` int64 [n_imp + 1]): every clicked candidate and ``ratio``
+    non-clicked ones per click, in a random order — MINDRecDatasetTrain._sample_candidates (reference mind_rec_dataset.py:13-77) as the
+    counter-based rule of include/manner_hip.h, a pure function of (seed, epoch, impression).  ``out_off`` int64 [B + 1] is the host's
+    prefix sum of ``p * (1 + ratio)`` and ``out_total`` its last element, so nothing is read back.
+    -> (rows int32 [out_total], labels f32 [out_total], users int64 [B] or None, positions int32 [out_total] or None).
+    A bad index or an ``out_off`` that disagrees with the labels raises through the device status word (``check_status``)."""
+    cand_rows = _dev(cand_rows, torch.int32, "cand_rows").contiguous()
+    labels = _dev(labels, torch.float32, "labels").contiguous()
+    cand_off = _dev(cand_off, torch.int64, "cand_off").contiguous()
+    imp_idx = _dev(imp_idx, torch.int64, "imp_idx").contiguous()
+    out_off = _dev(out_off, torch.int64, "out_off").contiguous()
+    nb, total = imp_idx.numel(), cand_rows.numel()
+    if labels.numel() != total or cand_off.numel() < 1 or out_off.numel() != nb + 1 or out_total < 0 or ratio < 0:
+        raise ValueError("sample_candidates: labels / cand_off / out_off do not fit cand_rows and imp_idx")
+    dev = cand_rows.device
+    if users is not None:
+        users = _dev(users, torch.int64, "users").contiguous()
+        if users.numel() != cand_off.numel() - 1:
+            raise ValueError("sample_candidates: users must hold one entry per impression")
+    rows = torch.empty((out_total,), dtype=torch.int32, device=dev)
+    lab = torch.empty((out_total,), dtype=torch.float32, device=dev)
+    pos = torch.empty((out_total,), dtype=torch.int32, device=dev) if return_pos else None
+    out_users = torch.empty((nb,), dtype=torch.int64, device=dev) if users is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().manner_hip_sample_candidates(
+            _ptr(cand_rows), _ptr(labels), _ptr(cand_off), cand_off.numel() - 1, total, _ptr(users), _ptr(imp_idx), nb, _ptr(out_off),
+            out_total, ratio, seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), _ptr(rows), _ptr(lab), _ptr(pos), _ptr(out_users),
+            _ptr(device_status(dev).word), _stream()))
+    return rows, lab, out_users, pos
+
+
+def gather_segments(src: Tensor, src_off: Tensor, imp_idx: Tensor, out_off: Tensor, out_total: int, src_f: Optional[Tensor] = None):
+    """Ragged gather: segment b of the result is segment ``imp_idx[b]`` of ``src`` (int32 [total], ``src_off`` int64 [n_seg + 1]);
+    ``out_off`` int64 [B + 1] / ``out_total`` are the host's prefix sum of the segment lengths.  ``src_f``: an f32 array gathered
+    alike.  -> out int32 [out_total] (, out_f f32 [out_total])."""
+    src = _dev(src, torch.int32, "src").contiguous()
+    src_off = _dev(src_off, torch.int64, "src_off").contiguous()
+    imp_idx = _dev(imp_idx, torch.int64, "imp_idx").contiguous()
+    out_off = _dev(out_off, torch.int64, "out_off").contiguous()
+    nb = imp_idx.numel()
+    if src_off.numel() < 1 or out_off.numel() != nb + 1 or out_total < 0:
+        raise ValueError("gather_segments: src_off / out_off do not fit imp_idx")
+    dev = src.device
+    if src_f is not None:
+        src_f = _dev(src_f, torch.float32, "src_f").contiguous()
+        if src_f.numel() != src.numel():
+            raise ValueError("gather_segments: src_f must have the size of src")
+    out = torch.empty((out_total,), dtype=torch.int32, device=dev)
+    out_f = torch.empty((out_total,), dtype=torch.float32, device=dev) if src_f is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().manner_hip_gather_segments(_ptr(src), _ptr(src_f), _ptr(src_off), src_off.numel() - 1, src.numel(),
+                                                          _ptr(imp_idx), nb, _ptr(out_off), out_total, _ptr(out), _ptr(out_f),
+                                                          _ptr(device_status(dev).word), _stream()))
+    return out if src_f is None else (out, out_f)
+
+
+def rows_max_len(store_len: Tensor, rows: Tensor, store_cnt: Optional[Tensor] = None) -> Tensor:
+    """Device int32 [2]: the longest stored news and (``store_cnt`` given) the longest entity list among the store rows ``rows``."""
+    store_len = _dev(store_len, torch.int32, "store_len").contiguous()
+    rows = _dev(rows, torch.int32, "rows").contiguous()
+    if store_cnt is not None:
+        store_cnt = _dev(store_cnt, torch.int32, "store_cnt").contiguous()
+    out = torch.empty((2,), dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.load().manner_hip_rows_max_len(_ptr(store_len), _ptr(store_cnt), store_len.numel(), _ptr(rows), rows.numel(),
+                                                       _ptr(out), _stream()))
+    return out
 
 
 def eval_loss(scores: Tensor, labels: Tensor, cand_off: Tensor, supcon: bool = True, temperature: float = 0.1,
