@@ -120,6 +120,15 @@ int launch_linear(const float* x, const int64_t* gather, int64_t n_src, const fl
                   int O, float* y, hipStream_t s, int32_t* status = nullptr) {
   if (R == 0) return MANNER_HIP_OK;
   if (K <= 0 || O <= 0 || K > 4096) return fail(MANNER_HIP_E_INVALID, "linear: K=%d O=%d unsupported (K <= 4096)", K, O);
+  if (K > 2048) {                                    // LIN_ROWS * K floats pass the 64 KiB a kernel gets without raising its limit
+    static bool lds_raised_dev[MAX_DEVICES] = {};
+    bool& lds_raised = lds_raised_dev[current_device_slot()];
+    if (!lds_raised) {
+      MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(linear_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         LIN_ROWS * 4096 * (int)sizeof(float)));                 // 128 KiB of the CU's 160
+      lds_raised = true;
+    }
+  }
   hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)((R + LIN_ROWS - 1) / LIN_ROWS)), dim3(256), LIN_ROWS * K * sizeof(float), s,
                      x, gather, n_src, W, b, R, K, O, y, status);
   MANNER_LAUNCH_CHECK();
