@@ -624,6 +624,40 @@ int manner_hip_mha_axis0(const float* x, int64_t L0, int64_t B1, int32_t E, int3
                          const float* in_proj_b, const float* out_proj_w, const float* out_proj_b, float* out, void* workspace,
                          size_t workspace_bytes, manner_hip_stream_t stream);
 
+/* ---- the MINER baseline's operators (csrc/poly.hip; f32, forward and backward; additive exports) -------------------------------------
+ * manner_hip_poly_attention replaces PolyAttention.forward (manner/models/components/attention.py:60-84): x [B, S, D],
+ * mask uint8 / bool [B, S], lin_w [Q, D] (no bias), codes [K, Q], bias f32 [B, S, T] or NULL; out [B, K, D] =
+ * softmax_s(tanh(x W^T) codes^T + mean_t bias) x.  As in the reference a masked slot's logit is 1e-30 (not -inf: it stays in the
+ * softmax) and the bias mean runs over all T columns.  S <= 256, K <= 64, Q <= 512, D <= 1024 (MANNER_HIP_E_INVALID otherwise).
+ * _backward: grad_x [B, S, D] (weighted-sum and projection routes), grad_w [Q, D], grad_codes [K, Q] from grad_out [B, K, D]; masked
+ * slots' logits receive no gradient; no gradient for bias.
+ * manner_hip_target_attention replaces TargetAwareAttention.forward (attention.py:102-116): query [B, K, D], key [B, C, D],
+ * value [B, C, K], lin_w [D, D] (no bias); out [B, C] = sum_k softmax_k(key . gelu(query W^T)^T) value.  K <= 64, D <= 1024.
+ * _backward: grad_query, grad_key, grad_value, grad_w from grad_out [B, C].
+ * manner_hip_bmm is DotProduct.forward (click_predictors.py:9-12) for M > 1 rows, as MINERModule.forward calls it
+ * (baselines/miner_module.py:195-198): out [B, M, N] = a [B, M, D] . b [B, D, N], b by element strides (read in place).
+ * _backward: grad_a [B, M, D], grad_b CONTIGUOUS [B, D, N].
+ * Every reduction across rows has a fixed order (no floating-point atomics).  Workspaces: the *_workspace_bytes queries. */
+size_t manner_hip_poly_attention_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t Q, int32_t K);
+int manner_hip_poly_attention(const float* x, const uint8_t* mask, const float* lin_w, const float* codes, const float* bias, int64_t T,
+                              int64_t B, int64_t S, int32_t D, int32_t Q, int32_t K, float* out, void* workspace, size_t workspace_bytes,
+                              manner_hip_stream_t stream);
+size_t manner_hip_poly_attention_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t Q, int32_t K);
+int manner_hip_poly_attention_backward(const float* x, const uint8_t* mask, const float* lin_w, const float* codes, const float* bias, int64_t T,
+                                       const float* grad_out, int64_t B, int64_t S, int32_t D, int32_t Q, int32_t K, float* grad_x, float* grad_w,
+                                       float* grad_codes, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+size_t manner_hip_target_attention_workspace_bytes(int64_t B, int32_t K, int32_t D);
+int manner_hip_target_attention(const float* query, const float* key, const float* value, const float* lin_w, int64_t B, int64_t C, int32_t K,
+                                int32_t D, float* out, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+size_t manner_hip_target_attention_backward_workspace_bytes(int64_t B, int32_t K, int32_t D);
+int manner_hip_target_attention_backward(const float* query, const float* key, const float* value, const float* lin_w, const float* grad_out,
+                                         int64_t B, int64_t C, int32_t K, int32_t D, float* grad_query, float* grad_key, float* grad_value,
+                                         float* grad_w, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+int manner_hip_bmm(const float* a, const float* b, int64_t B, int64_t M, int64_t N, int32_t D, int64_t b_stride_b, int64_t b_stride_d,
+                   int64_t b_stride_n, float* out, manner_hip_stream_t stream);
+int manner_hip_bmm_backward(const float* grad_out, const float* a, const float* b, int64_t B, int64_t M, int64_t N, int32_t D, int64_t b_stride_b,
+                            int64_t b_stride_d, int64_t b_stride_n, float* grad_a, float* grad_b, manner_hip_stream_t stream);
+
 /* ---- content-addressed news-embedding cache (ABI v6, round 4; csrc/cache.hip) ----------------------------------------------
  * SURVEY.md §8(d) mode T ("each unique news encoded once per module") behind the unchanged drop-in call pattern: the reference
  * re-encodes every occurrence — manner/models/cr_module.py:107,113 call manner/models/components/news_encoder.py:29-37 per batch —

@@ -119,6 +119,16 @@ SIGNATURES = {
                                                _P, _P, _P]),
     "manner_hip_gather_segments": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P]),
     "manner_hip_rows_max_len": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "manner_hip_poly_attention_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),
+    "manner_hip_poly_attention": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _SZ, _P]),
+    "manner_hip_poly_attention_backward_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),
+    "manner_hip_poly_attention_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_target_attention_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "manner_hip_target_attention": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _SZ, _P]),
+    "manner_hip_target_attention_backward_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "manner_hip_target_attention_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_bmm": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _I64, _I64, _I64, _P, _P]),
+    "manner_hip_bmm_backward": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _I64, _I64, _I64, _P, _P, _P]),
 }
 
 _lib = None

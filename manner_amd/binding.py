@@ -13,7 +13,7 @@ them, exactly the classes this build mirrors:
 
 Everything else of those files — ``NAMLNewsEncoder``, ``LSTURNewsEncoder``, ``MINERNewsEncoder``, ``CAUMNewsEncoder``,
 ``PolyAttention``, ``TargetAwareAttention``, ``DenseAttention``, ``LSTURUserEncoder``, ``CAUMUserEncoder``, ``MINSUserEncoder`` —
-stays the reference's own torch code, and so do the names those classes captured at import time (the reference's
+stays the reference's own torch code by default, and so do the names those classes captured at import time (the reference's
 ``NAMLNewsEncoder`` keeps using the reference's ``AdditiveAttention``: its module-level binding inside ``news_encoder`` is an import
 of the ORIGINAL class object and is only replaced where it is one of the listed names of that module).  ``manner.utils``,
 ``manner.data``, ``manner.models.cr_module`` … are never touched: there is no ``manner`` package in this repository that could
@@ -23,9 +23,21 @@ Modules of the reference imported BEFORE ``install()`` (say ``manner.models.cr_m
 ``from … import MannerNewsEncoder``) are patched too: every module named ``manner`` / ``manner.*`` whose globals hold one of the
 replaced class objects — under any alias, e.g. ``UserEncoder`` — is rebound, so the call order does not matter.
 
+Opt-in baselines: ``install(baselines=("miner",))`` additionally rebinds the three leaf classes of the MINER baseline
+(reference manner/models/baselines/miner_module.py:19-22 imports them as ``NewsEncoder``, ``UserEncoder`` and
+``TargetAwareAttention``; its ``DotProduct`` is rebound already, and the mirror serves MINER's ``[B, C, D] x [B, D, K]`` call):
+
+    news_encoder      MINERNewsEncoder
+    attention         PolyAttention, TargetAwareAttention
+
+``MINERModule`` itself is not mirrored: its category-bias construction, ``pairwise_cosine_similarity``, the max / mean aggregation
+and the disagreement loss are Lightning-level code and stay the reference's torch.  A plain ``install()`` binds exactly the first
+table, whatever an earlier call added stays until ``uninstall()``.
+
 Use (no reference source line changes):
 
     python -m manner_amd.run manner/train.py experiment=cr_module_mind_title_scl_lf      # = install() + runpy of the script
+    python -m manner_amd.run --baselines miner manner/train.py experiment=miner_weighted_mind
 
 or two lines at the top of ``manner/train.py`` / ``manner/eval.py``:  ``import manner_amd; manner_amd.install()``.
 """
@@ -33,7 +45,7 @@ from __future__ import annotations
 
 import importlib
 import sys
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 TARGETS = {
     "news_encoder": ("MannerTextEncoder", "MannerEntityEncoder", "MannerNewsEncoder", "PLMTextEncoder"),
@@ -41,20 +53,38 @@ TARGETS = {
     "user_encoder": ("NAMLUserEncoder", "NRMSUserEncoder"),
     "click_predictors": ("DotProduct",),
 }
+BASELINE_TARGETS = {
+    "miner": {"news_encoder": ("MINERNewsEncoder",), "attention": ("PolyAttention", "TargetAwareAttention")},
+}
 _REF_PKG = "manner.models.components"
 _MIRROR_PKG = "manner_amd.models.components"
 _installed: Dict[str, Dict[str, type]] = {}          # module name -> {class name: the reference's original class}
 
 
-def install(reference_root: Optional[str] = None) -> Dict[str, List[str]]:
+def _targets(baselines: Sequence[str]) -> Dict[str, Tuple[str, ...]]:
+    if isinstance(baselines, str):
+        baselines = (baselines,)
+    unknown = [b for b in baselines if b not in BASELINE_TARGETS]
+    if unknown:
+        raise ValueError(f"manner_amd.install(): unknown baseline {unknown[0]!r} (known: {', '.join(sorted(BASELINE_TARGETS))})")
+    targets = dict(TARGETS)
+    for b in baselines:
+        for leaf, names in BASELINE_TARGETS[b].items():
+            targets[leaf] = targets.get(leaf, ()) + tuple(n for n in names if n not in targets.get(leaf, ()))
+    return targets
+
+
+def install(reference_root: Optional[str] = None, baselines: Sequence[str] = ()) -> Dict[str, List[str]]:
     """Rebind the mirrored classes inside the reference's ``manner.models.components`` modules.  ``reference_root``: a checkout
-    of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  Returns {module: [rebound names]} (also
-    the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
+    of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  ``baselines``: opt-in sets of further classes
+    (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention); an unknown name raises ValueError.  Returns {module: [rebound
+    names]} (also the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
+    targets = _targets(baselines)
     if reference_root and reference_root not in sys.path:
         sys.path.insert(0, reference_root)
     report: Dict[str, List[str]] = {}
     swaps = {}                                       # id(original class) -> mirror class
-    for leaf, names in TARGETS.items():
+    for leaf, names in targets.items():
         try:
             ref_mod = importlib.import_module(f"{_REF_PKG}.{leaf}")
         except ModuleNotFoundError as e:
@@ -78,7 +108,7 @@ def install(reference_root: Optional[str] = None) -> Dict[str, List[str]]:
             report.setdefault(ref_mod.__name__, []).append(n)
     # aliases captured by reference modules that were imported before install(): patch by object identity
     if swaps:
-        own = {f"{_REF_PKG}.{leaf}" for leaf in TARGETS}
+        own = {f"{_REF_PKG}.{leaf}" for leaf in targets}
         for name, mod in list(sys.modules.items()):
             if mod is None or not (name == "manner" or name.startswith("manner.")) or name in own:
                 continue

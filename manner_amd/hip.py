@@ -726,6 +726,85 @@ def dot(user: Tensor, cand: Tensor) -> Tensor:
     return out
 
 
+def _workspace(nbytes: int, device) -> Tensor:
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _mask_bytes(mask: Tensor, shape, name: str) -> Tensor:
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor — the MANNeR HIP hot path has no CPU fallback")
+    if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != tuple(shape):
+        raise TypeError(f"{name}: expected bool or uint8 {tuple(shape)}, got {mask.dtype} {tuple(mask.shape)}")
+    return mask.contiguous()
+
+
+def poly_attention(x: Tensor, mask: Tensor, lin_w: Tensor, codes: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """PolyAttention.forward (reference attention.py:60-84): x [B, S, D], mask bool [B, S], linear.weight [Q, D], context_codes
+    [K, Q], bias [B, S, T] or None -> [B, K, D].  A masked slot keeps the logit 1e-30 and the bias mean runs over all T columns,
+    as in the reference.  S <= 256, K <= 64, Q <= 512, D <= 1024 (the library refuses anything else)."""
+    x = _dev(x, torch.float32, "clicked_news_vector").contiguous()
+    b, s, d = x.shape
+    mask = _mask_bytes(mask, (b, s), "attn_mask")
+    lin_w = _dev(lin_w, torch.float32, "linear.weight").contiguous()
+    codes = _dev(codes, torch.float32, "context_codes").contiguous()
+    q, k = lin_w.shape[0], codes.shape[0]
+    assert lin_w.shape == (q, d) and codes.shape == (k, q)
+    t = 0
+    if bias is not None:
+        bias = _dev(bias, torch.float32, "bias").contiguous()
+        assert bias.dim() == 3 and bias.shape[:2] == (b, s)
+        t = bias.shape[2]
+    out = torch.empty((b, k, d), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.manner_hip_poly_attention_workspace_bytes(b, s, d, q, k))
+        ws = _workspace(need, x.device)
+        _lib.check(lib.manner_hip_poly_attention(_ptr(x), _ptr(mask), _ptr(lin_w), _ptr(codes), _ptr(bias), t, b, s, d, q, k, _ptr(out),
+                                                 _ptr(ws), need, _stream()))
+    return out
+
+
+def target_attention(query: Tensor, key: Tensor, value: Tensor, lin_w: Tensor) -> Tensor:
+    """TargetAwareAttention.forward (reference attention.py:102-116): query [B, K, D], key [B, C, D], value [B, C, K],
+    linear.weight [D, D] -> [B, C].  K <= 64, D <= 1024."""
+    query = _dev(query, torch.float32, "query").contiguous()
+    key = _dev(key, torch.float32, "key").contiguous()
+    value = _dev(value, torch.float32, "value").contiguous()
+    lin_w = _dev(lin_w, torch.float32, "linear.weight").contiguous()
+    b, k, d = query.shape
+    c = key.shape[1]
+    assert key.shape == (b, c, d) and value.shape == (b, c, k) and lin_w.shape == (d, d)
+    out = torch.empty((b, c), dtype=torch.float32, device=query.device)
+    lib = _lib.load()
+    with torch.cuda.device(query.device):
+        need = int(lib.manner_hip_target_attention_workspace_bytes(b, k, d))
+        ws = _workspace(need, query.device)
+        _lib.check(lib.manner_hip_target_attention(_ptr(query), _ptr(key), _ptr(value), _ptr(lin_w), b, c, k, d, _ptr(out), _ptr(ws), need,
+                                                   _stream()))
+    return out
+
+
+def _strided_operand(t: Tensor) -> Tensor:
+    """A [B, D, N] operand the kernels may read in place: non-negative strides, D or N contiguous."""
+    if min(t.stride()) < 0 or (t.stride(1) != 1 and t.stride(2) != 1):
+        return t.contiguous()
+    return t
+
+
+def bmm(a: Tensor, b: Tensor) -> Tensor:
+    """DotProduct's ``torch.bmm`` for M > 1 rows, as MINERModule.forward calls it (reference baselines/miner_module.py:195-198):
+    a [B, M, D], b [B, D, N] (any strides, e.g. a permuted [B, N, D], read in place) -> [B, M, N]."""
+    a = _dev(a, torch.float32, "clicked_news_vector").contiguous()
+    b = _strided_operand(_dev(b, torch.float32, "candidate_news_vector"))
+    bsz, m, d = a.shape
+    assert b.dim() == 3 and b.shape[0] == bsz and b.shape[1] == d
+    n = b.shape[2]
+    out = torch.empty((bsz, m, n), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().manner_hip_bmm(_ptr(a), _ptr(b), bsz, m, n, d, b.stride(0), b.stride(1), b.stride(2), _ptr(out), _stream()))
+    return out
+
+
 class HalfTable:
     """IEEE-half copy of a news-embedding table for the scorer: ``rows`` float16 [n, D] and, when centred, ``mean`` float32 [D]
     (rows = half(T - mean)); see ``table_to_f16``."""

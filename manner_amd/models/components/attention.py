@@ -1,4 +1,7 @@
-"""AdditiveAttention — mirror of reference manner/models/components/attention.py:6-29."""
+"""AdditiveAttention, PolyAttention, TargetAwareAttention — mirrors of reference manner/models/components/attention.py:6-29, 32-84,
+87-116 (the latter two are MINER's; ``install(baselines=("miner",))`` binds them)."""
+from typing import Optional
+
 import torch
 import torch.nn as nn
 
@@ -18,3 +21,36 @@ class AdditiveAttention(nn.Module):
             return train.additive_pool(input_vector, self.linear.weight, self.linear.bias, self.query)      # with its backward
         return hip.additive_pool(input_vector, self.linear.weight.detach(), self.linear.bias.detach(),
                                  self.query.detach())
+
+
+def _differentiable(module: nn.Module, *inputs: torch.Tensor) -> bool:
+    """The rule of AdditiveAttention.forward: autograd records the forward whenever the reference's torch ops would."""
+    return torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or any(p.requires_grad for p in module.parameters()))
+
+
+class PolyAttention(nn.Module):
+    def __init__(self, input_embed_dim: int, num_context_codes: int, context_code_dim: int) -> None:
+        super().__init__()
+        self.linear = nn.Linear(in_features=input_embed_dim, out_features=context_code_dim, bias=False)
+        self.context_codes = nn.Parameter(nn.init.xavier_uniform_(torch.empty(num_context_codes, context_code_dim),
+                                                                  gain=nn.init.calculate_gain("tanh")))
+
+    def forward(self, clicked_news_vector: torch.Tensor, attn_mask: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(batch, hist, dim), (batch, hist) bool, (batch, hist, candidates of the batch) or None -> (batch, codes, dim); a masked slot
+        keeps the logit 1e-30 and the bias mean runs over all its columns, as in the reference."""
+        if _differentiable(self, clicked_news_vector):
+            return train.poly_attention(clicked_news_vector, attn_mask, self.linear.weight, self.context_codes, bias)
+        return hip.poly_attention(clicked_news_vector, attn_mask, self.linear.weight.detach(), self.context_codes.detach(),
+                                  None if bias is None else bias.detach())
+
+
+class TargetAwareAttention(nn.Module):
+    def __init__(self, input_embed_dim: int) -> None:
+        super().__init__()
+        self.linear = nn.Linear(in_features=input_embed_dim, out_features=input_embed_dim, bias=False)
+
+    def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor) -> torch.Tensor:
+        """(batch, codes, dim), (batch, candidates, dim), (batch, candidates, codes) -> (batch, candidates)"""
+        if _differentiable(self, query, key, value):
+            return train.target_attention(query, key, value, self.linear.weight)
+        return hip.target_attention(query, key, value, self.linear.weight.detach())

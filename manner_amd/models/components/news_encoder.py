@@ -1,5 +1,5 @@
-"""MannerTextEncoder / MannerEntityEncoder / MannerNewsEncoder — mirror of reference
-manner/models/components/news_encoder.py:11-129.
+"""MannerTextEncoder / MannerEntityEncoder / MannerNewsEncoder / PLMTextEncoder / MINERNewsEncoder — mirror of reference
+manner/models/components/news_encoder.py:11-171, 297-328.
 
 Same constructor arguments, forward signature and state_dict keys (``text_encoder.plm_model.*`` are
 the HF BertModel / RobertaModel names), so reference checkpoints load with
@@ -405,8 +405,12 @@ class MannerTextEncoder(nn.Module):
                     ph = pc.hidden_states(engine, ids, mask, start, tp)
                 extra = dict(prefix_hidden=ph, start_layer=start)
         return train.encode_train(plm.cfg, params, ids, mask, precision=tp, p_hidden=on * plm.hidden_dropout_prob,
-                                  p_attn=on * plm.attention_probs_dropout_prob, p_out=on * self.dropout.p, seed=seed, prefix_engine=engine,
+                                  p_attn=on * plm.attention_probs_dropout_prob, p_out=on * self._cls_dropout_p(), seed=seed, prefix_engine=engine,
                                   max_len=self.train_max_length, **extra)
+
+    def _cls_dropout_p(self) -> float:
+        """Probability of the dropout on the [CLS] vector itself in train() mode (news_encoder.py:35)."""
+        return self.dropout.p
 
     #: Opt-in: the longest padded batch train() accepts.  128 (the default) keeps the short-row limit; up to 512 trains on news of
     #: 129..512 tokens (a higher data.tokenizer_max_length), whose attention runs the long-row kernels.  Saved activations grow per
@@ -543,6 +547,38 @@ class MannerTextEncoder(nn.Module):
         with torch.no_grad():
             mode = self.resolved_precision()
             return self._encoder(ids.device, mode).encode_hidden(ids, mask, n_layers, precision=mode, out_dtype=dtype)
+
+
+class MINERNewsEncoder(MannerTextEncoder):
+    """reference news_encoder.py:297-328 — MINER's news encoder: the [CLS] vector of the PLM, then (``apply_reduce_dim``) a Linear to
+    ``news_embedding_dim`` and a dropout.  State-dict keys ``plm_model.*``, ``reduce_dim.weight``, ``reduce_dim.bias``.
+
+    The [CLS] engines, the precision rule, the caches and the handle invalidation are MannerTextEncoder's (this is a subclass);
+    unlike that class the reference applies NO dropout to the [CLS] vector itself here (news_encoder.py:319-326)."""
+
+    def __init__(self, plm_model: str, frozen_layers: List[int], apply_reduce_dim: bool, text_embedding_dim: int, news_embedding_dim: int,
+                 dropout_probability: float) -> None:
+        super().__init__(plm_model=plm_model, frozen_layers=frozen_layers, dropout_probability=dropout_probability)
+        self.apply_reduce_dim = apply_reduce_dim
+        if self.apply_reduce_dim:
+            self.reduce_dim = nn.Linear(in_features=text_embedding_dim, out_features=news_embedding_dim)
+        else:
+            del self.dropout                                 # the reference builds it with reduce_dim only
+
+    def _cls_dropout_p(self) -> float:
+        return 0.0
+
+    def forward(self, tokenized_text) -> torch.Tensor:
+        text_vector = super().forward(tokenized_text)
+        if not self.apply_reduce_dim:
+            return text_vector
+        lin = self.reduce_dim
+        if self.training or _wants_graph(lin, text_vector):
+            out = train.linear(text_vector, lin.weight, lin.bias)
+            if self.training and self.dropout.p > 0.0:
+                out = train.dropout(out, self.dropout.p, int(torch.randint(0, 2 ** 62, (1,)).item()), site=6)
+            return out
+        return hip.linear(text_vector, lin.weight.detach(), lin.bias.detach())
 
 
 class MannerEntityEncoder(nn.Module):

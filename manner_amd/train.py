@@ -412,6 +412,32 @@ def dot(user: Tensor, cand: Tensor) -> Tensor:
     return _Dot.apply(hip._dev(user, torch.float32, "user_vector"), hip._dev(cand, torch.float32, "candidate_news_vector"))
 
 
+class _Bmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a: Tensor, b: Tensor):
+        ctx.save_for_backward(a, b)
+        return hip.bmm(a.detach(), b.detach())
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        a, b = ctx.saved_tensors
+        bsz, m, d = a.shape
+        n = b.shape[2]
+        da = torch.empty((bsz, m, d), dtype=torch.float32, device=a.device)
+        db = torch.empty((bsz, d, n), dtype=torch.float32, device=a.device)
+        with torch.cuda.device(a.device):
+            g, ac, bs = _f32(g, "grad"), a.contiguous(), hip._strided_operand(b)
+            _lib.check(_lib.load().manner_hip_bmm_backward(hip._ptr(g), hip._ptr(ac), hip._ptr(bs), bsz, m, n, d, bs.stride(0), bs.stride(1),
+                                                           bs.stride(2), hip._ptr(da), hip._ptr(db), hip._stream()))
+        return da, db
+
+
+def bmm(a: Tensor, b: Tensor) -> Tensor:
+    """DotProduct.forward's ``torch.bmm`` for M > 1 rows (MINERModule.forward, baselines/miner_module.py:195-198) with autograd:
+    a [B, M, D], b [B, D, N] (any strides) -> [B, M, N]."""
+    return _Bmm.apply(hip._dev(a, torch.float32, "clicked_news_vector"), hip._dev(b, torch.float32, "candidate_news_vector"))
+
+
 class _Loss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores: Tensor, labels: Tensor, cand_off: Tensor, mode: int, temperature: float, c_max: int):
@@ -509,6 +535,69 @@ class _AdditivePool(torch.autograd.Function):
 def additive_pool(x: Tensor, lin_w: Tensor, lin_b: Tensor, query: Tensor) -> Tensor:
     """AdditiveAttention.forward (attention.py:21-27) with autograd: x [B, S, D] -> [B, D]."""
     return _AdditivePool.apply(_f32(x, "input_vector"), _f32(lin_w, "linear.weight"), _f32(lin_b, "linear.bias"), _f32(query, "query"))
+
+
+class _PolyAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, mask: Tensor, lin_w: Tensor, codes: Tensor, bias: Optional[Tensor]):
+        ctx.save_for_backward(x, mask, lin_w, codes, bias)
+        return hip.poly_attention(x, mask, lin_w, codes, bias)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, mask, lin_w, codes, bias = ctx.saved_tensors      # the backward recomputes the weights from the pre-activations
+        b, s, d = x.shape
+        q, k = lin_w.shape[0], codes.shape[0]
+        lib = _lib.load()
+        dx, dw, dc = torch.empty_like(x), torch.empty_like(lin_w), torch.empty_like(codes)
+        with torch.cuda.device(x.device):
+            need = int(lib.manner_hip_poly_attention_backward_workspace_bytes(b, s, d, q, k))
+            ws = hip._workspace(need, x.device)
+            g = _f32(g, "grad")
+            _lib.check(lib.manner_hip_poly_attention_backward(hip._ptr(x), hip._ptr(mask), hip._ptr(lin_w), hip._ptr(codes), hip._ptr(bias),
+                                                              0 if bias is None else bias.shape[2], hip._ptr(g), b, s, d, q, k, hip._ptr(dx),
+                                                              hip._ptr(dw), hip._ptr(dc), hip._ptr(ws), need, hip._stream()))
+        return dx, None, dw, dc, None
+
+
+def poly_attention(x: Tensor, mask: Tensor, lin_w: Tensor, codes: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """PolyAttention.forward (attention.py:60-84) with autograd for x, linear.weight and context_codes: x [B, S, D] -> [B, K, D].
+    No gradient is built for ``bias`` (MINERModule feeds it from a frozen embedding): one that requires it is refused."""
+    if bias is not None:
+        if bias.requires_grad:
+            raise RuntimeError("poly_attention: no gradient is built for `bias` (MINERModule's category bias comes from a frozen embedding)")
+        bias = _f32(bias, "bias")
+    x = _f32(x, "clicked_news_vector")
+    mask = hip._mask_bytes(mask, x.shape[:2], "attn_mask")
+    return _PolyAttention.apply(x, mask, _f32(lin_w, "linear.weight"), _f32(codes, "context_codes"), bias)
+
+
+class _TargetAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query: Tensor, key: Tensor, value: Tensor, lin_w: Tensor):
+        ctx.save_for_backward(query, key, value, lin_w)
+        return hip.target_attention(query, key, value, lin_w)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        query, key, value, lin_w = ctx.saved_tensors
+        b, k, d = query.shape
+        c = key.shape[1]
+        lib = _lib.load()
+        dq, dk, dv, dw = torch.empty_like(query), torch.empty_like(key), torch.empty_like(value), torch.empty_like(lin_w)
+        with torch.cuda.device(query.device):
+            need = int(lib.manner_hip_target_attention_backward_workspace_bytes(b, k, d))
+            ws = hip._workspace(need, query.device)
+            g = _f32(g, "grad")
+            _lib.check(lib.manner_hip_target_attention_backward(hip._ptr(query), hip._ptr(key), hip._ptr(value), hip._ptr(lin_w), hip._ptr(g), b, c,
+                                                                k, d, hip._ptr(dq), hip._ptr(dk), hip._ptr(dv), hip._ptr(dw), hip._ptr(ws), need,
+                                                                hip._stream()))
+        return dq, dk, dv, dw
+
+
+def target_attention(query: Tensor, key: Tensor, value: Tensor, lin_w: Tensor) -> Tensor:
+    """TargetAwareAttention.forward (attention.py:102-116) with autograd: query [B, K, D], key [B, C, D], value [B, C, K] -> [B, C]."""
+    return _TargetAttention.apply(_f32(query, "query"), _f32(key, "key"), _f32(value, "value"), _f32(lin_w, "linear.weight"))
 
 
 class _Axis0Attention(torch.autograd.Function):
