@@ -658,6 +658,45 @@ int manner_hip_bmm(const float* a, const float* b, int64_t B, int64_t M, int64_t
 int manner_hip_bmm_backward(const float* grad_out, const float* a, const float* b, int64_t B, int64_t M, int64_t N, int32_t D, int64_t b_stride_b,
                             int64_t b_stride_d, int64_t b_stride_n, float* grad_a, float* grad_b, manner_hip_stream_t stream);
 
+/* ---- the CAUM baseline's operators (csrc/caum.hip; f32, forward and backward; additive exports) -------------------------------------
+ * manner_hip_axis0_attention_any is manner_hip_axis0_attention at ANY head dim 1 <= E / heads <= 64 (CAUM ships 25 and 5): qkv
+ * [L0, B1, 3E] -> out [L0, B1, E], attention along axis 0.  stats [L0 * B1 * heads * 3] (may be NULL in the forward) receives the
+ * softmax {max, sum} of every (row, slot, head); _backward_q reads them with the forward's `out`, writes the q third of grad_qkv and
+ * the third statistic (d out . out); _backward_kv, called after it, writes the k and v thirds.
+ * manner_hip_caum_user_forward is CAUMUserEncoder.forward (manner/models/components/user_encoder.py:121-178) for one candidate per
+ * user: x [B, S, D], c [B, D] with rows c_stride floats apart (the cand[:, i, :] view), out [B].  params: the 16 tensors linear1.weight
+ * [F, 4D], .bias, linear2.weight [U, 2D], .bias, multihead_attention.in_proj_weight [3U, U], in_proj_bias, out_proj.weight [U, U],
+ * .bias, linear3.weight [U, F + U], .bias, dense_att.linear.weight [H1, 2U], .bias, dense_att.linear2.weight [H2, H1], .bias,
+ * dense_att.linear3.weight [1, H2], .bias, in that order.  p > 0: the three dropouts on the generator of manner_hip_dropout_mask at
+ * the sites site0 (candidate, element b * D + d), site0 + 1 (clicked news, flat index) and site0 + 2 (cat[cnn, self], flat index over
+ * [B S, F + U]).  The attention runs across the B users at each history slot and the softmax over all S slots, unmasked, as in the
+ * reference.  S <= 256; D, F, U, H1, H2 <= 1024; U / heads <= 64; D == U (MANNER_HIP_E_INVALID otherwise).  `saved`
+ * (manner_hip_caum_user_saved_bytes) keeps the activations for _backward, which fills grad_x [B, S, D], grad_c [B, D] (contiguous) and
+ * the 16 parameter gradients; the K third of d in_proj_bias and d dense_att.linear3.bias, zero in exact arithmetic, are written as zeros.
+ * manner_hip_relu / _backward: out = max(x, 0); grad_x = grad_out where x > 0.
+ * Every reduction across rows has a fixed order (no floating-point atomics). */
+int manner_hip_axis0_attention_any(const float* qkv, int64_t L0, int64_t B1, int32_t E, int32_t heads, float* out, float* stats,
+                                   manner_hip_stream_t stream);
+int manner_hip_axis0_attention_any_backward_q(const float* qkv, const float* out, const float* grad_out, int64_t L0, int64_t B1, int32_t E,
+                                              int32_t heads, float* grad_qkv, float* stats, manner_hip_stream_t stream);
+int manner_hip_axis0_attention_any_backward_kv(const float* qkv, const float* grad_out, const float* stats, int64_t L0, int64_t B1, int32_t E,
+                                               int32_t heads, float* grad_qkv, manner_hip_stream_t stream);
+size_t manner_hip_caum_user_saved_bytes(int64_t B, int64_t S, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads);
+int manner_hip_caum_user_forward(const float* x, const float* c, int64_t c_stride, const float* const* params, int64_t B, int64_t S, int32_t D,
+                                 int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads, float p, uint64_t seed, uint32_t site0, float* out,
+                                 void* saved, size_t saved_bytes, manner_hip_stream_t stream);
+size_t manner_hip_caum_user_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads);
+int manner_hip_caum_user_backward(const float* const* params, const float* grad_out, int64_t B, int64_t S, int32_t D, int32_t F, int32_t U,
+                                  int32_t H1, int32_t H2, int32_t heads, float p, uint64_t seed, uint32_t site0, void* saved, size_t saved_bytes,
+                                  float* grad_x, float* grad_c, float* const* grads, void* workspace, size_t workspace_bytes,
+                                  manner_hip_stream_t stream);
+/* DenseAttention alone (attention.py:134-141): y [R, O] = tanh(x W^T + b), and grad_pre = grad_out (1 - y^2) for its backward */
+int manner_hip_linear_tanh(const float* x, const float* weight, const float* bias, int64_t R, int32_t K, int32_t O, float* y,
+                           manner_hip_stream_t stream);
+int manner_hip_tanh_backward(const float* y, const float* grad_out, float* grad_pre, int64_t n, manner_hip_stream_t stream);
+int manner_hip_relu(const float* x, float* out, int64_t n, manner_hip_stream_t stream);
+int manner_hip_relu_backward(const float* x, const float* grad_out, float* grad_x, int64_t n, manner_hip_stream_t stream);
+
 /* ---- content-addressed news-embedding cache (ABI v6, round 4; csrc/cache.hip) ----------------------------------------------
  * SURVEY.md §8(d) mode T ("each unique news encoded once per module") behind the unchanged drop-in call pattern: the reference
  * re-encodes every occurrence — manner/models/cr_module.py:107,113 call manner/models/components/news_encoder.py:29-37 per batch —

@@ -129,6 +129,19 @@ SIGNATURES = {
     "manner_hip_target_attention_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "manner_hip_bmm": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _I64, _I64, _I64, _P, _P]),
     "manner_hip_bmm_backward": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _I64, _I64, _I64, _P, _P, _P]),
+    "manner_hip_axis0_attention_any": (C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    "manner_hip_axis0_attention_any_backward_q": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    "manner_hip_axis0_attention_any_backward_kv": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P]),
+    "manner_hip_caum_user_saved_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "manner_hip_caum_user_forward": (C.c_int, [_P, _P, _I64, C.POINTER(_P), _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, C.c_float,
+                                               C.c_uint64, C.c_uint32, _P, _P, _SZ, _P]),
+    "manner_hip_caum_user_backward_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "manner_hip_caum_user_backward": (C.c_int, [C.POINTER(_P), _P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, C.c_float, C.c_uint64,
+                                                C.c_uint32, _P, _SZ, _P, _P, C.POINTER(_P), _P, _SZ, _P]),
+    "manner_hip_linear_tanh": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P]),
+    "manner_hip_tanh_backward": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "manner_hip_relu": (C.c_int, [_P, _P, _I64, _P]),
+    "manner_hip_relu_backward": (C.c_int, [_P, _P, _P, _I64, _P]),
 }
 
 _lib = None

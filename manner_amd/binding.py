@@ -30,6 +30,15 @@ Opt-in baselines: ``install(baselines=("miner",))`` additionally rebinds the thr
     news_encoder      MINERNewsEncoder
     attention         PolyAttention, TargetAwareAttention
 
+``install(baselines=("caum_plm",))`` (the reference's config and module name, configs/model/caum_plm.yaml) rebinds the four leaf classes
+of the CAUM baseline (baselines/caum_plm_module.py:15-16 imports ``CAUMNewsEncoder`` and ``CAUMUserEncoder``; they build the other two):
+
+    news_encoder      CAUMCategoryEncoder, CAUMNewsEncoder
+    user_encoder      CAUMUserEncoder
+    attention         DenseAttention
+
+``CAUMPLMModule``'s own lines — the per-candidate loop, ``to_dense_batch``, the loss, the metrics — stay the reference's torch.
+
 ``MINERModule`` itself is not mirrored: its category-bias construction, ``pairwise_cosine_similarity``, the max / mean aggregation
 and the disagreement loss are Lightning-level code and stay the reference's torch.  A plain ``install()`` binds exactly the first
 table, whatever an earlier call added stays until ``uninstall()``.
@@ -55,6 +64,8 @@ TARGETS = {
 }
 BASELINE_TARGETS = {
     "miner": {"news_encoder": ("MINERNewsEncoder",), "attention": ("PolyAttention", "TargetAwareAttention")},
+    "caum_plm": {"news_encoder": ("CAUMCategoryEncoder", "CAUMNewsEncoder"), "user_encoder": ("CAUMUserEncoder",),
+                 "attention": ("DenseAttention",)},
 }
 _REF_PKG = "manner.models.components"
 _MIRROR_PKG = "manner_amd.models.components"
@@ -77,7 +88,8 @@ def _targets(baselines: Sequence[str]) -> Dict[str, Tuple[str, ...]]:
 def install(reference_root: Optional[str] = None, baselines: Sequence[str] = ()) -> Dict[str, List[str]]:
     """Rebind the mirrored classes inside the reference's ``manner.models.components`` modules.  ``reference_root``: a checkout
     of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  ``baselines``: opt-in sets of further classes
-    (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention); an unknown name raises ValueError.  Returns {module: [rebound
+    (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention; ``"caum_plm"``: CAUMCategoryEncoder, CAUMNewsEncoder,
+    CAUMUserEncoder, DenseAttention); an unknown name raises ValueError.  Returns {module: [rebound
     names]} (also the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
     targets = _targets(baselines)
     if reference_root and reference_root not in sys.path:

@@ -1,0 +1,925 @@
+// The operators of the CAUM baseline (reference manner/models/baselines/caum_plm_module.py), f32, forward and backward:
+//   CAUMUserEncoder.forward (manner/models/components/user_encoder.py:121-178) with its DenseAttention (attention.py:119-141)
+//   axis-0 multi-head attention at ANY head dim 1..64 (CAUM ships 25 in the user encoder and 5 in the entity encoder)
+//   ReLU (CAUMCategoryEncoder, news_encoder.py:350-355)
+// One call scores ONE candidate per user: x [B, S, D] clicked news, c [B, D] candidate -> out [B].  The concatenated operands of the
+// reference are never built by torch: a pack kernel writes the window operand [x[s-1], x[s], x[s+1], c] and [c, x[s]] once, the
+// producers of cat[cnn, self] write into the two column ranges of one buffer, and the candidate half of the dense attention's first
+// Linear is computed once per user.  nn.MultiheadAttention is batch_first=False but fed [B, S, U]: attention runs ACROSS THE B USERS
+// of the call at each history slot (as in the reference's other batch_first=False calls), so B is the key axis.
+// The workload is small (B = 8, S = 50, widths 400) and latency-bound: plain f32 VALU kernels.  Every reduction across rows runs in a
+// fixed order (no floating-point atomics): two runs give the same bits.
+#include <math.h>
+
+#include <algorithm>
+
+#include "train_common.h"
+
+namespace manner {
+namespace {
+
+constexpr int CA_MAX_S = 256, CA_MAX_W = 1024, CA_MAX_DH = 64;
+constexpr int CA_BLOCK = 256, CA_WAVE = 64, CA_WAVES = CA_BLOCK / CA_WAVE;      // threads per workgroup, lanes per wave, waves per workgroup
+constexpr int CA_FLAT_GRID = 8192;   // most workgroups of a grid-stride elementwise launch
+constexpr int CA_ALIGN = 64;         // floats every saved / workspace buffer is aligned to
+constexpr int CA_ROWS = 8;       // rows per workgroup of the linear, data-gradient, score and row kernels
+constexpr int CA_OT = 64;        // output features per workgroup of the linear kernel
+constexpr int CA_KS = 128;       // input features per step of the linear kernel (x rows 4 KiB, weight tile CA_OT x (CA_KS + 1) floats = 32 KiB)
+constexpr int CA_OC = 1024;      // output features staged per pass of the data-gradient kernel (32 KiB)
+constexpr int CA_LDS = 7168;     // floats of each of the two staged attention operands (2 x 28 KiB)
+constexpr int CA_KT = 64;        // rows of the other side per tile when a (slot, head) pair does not fit CA_LDS or B > 256
+constexpr int WG_MAX_GROUPS = 16, WG_ROWS = 64;      // weight gradient: row groups, least rows per group (the scheme of poly.hip)
+constexpr int CS_COLS = 64, CS_GROUPS = 16;          // bias gradient: columns per workgroup, row groups (as train_small.hip)
+static_assert(CA_KT * CA_MAX_DH <= CA_LDS, "a tile of the largest head fits");
+static_assert(CA_OT * CA_WAVES == CA_BLOCK && CA_WAVES == 4 && CA_KS % CA_WAVES == 0, "lin_kernel: thread = (output feature, K quarter)");
+static_assert(CA_MAX_S % CA_WAVE == 0, "one wave holds a user's scores, CA_MAX_S / CA_WAVE per lane");
+static_assert(CA_KT <= CA_BLOCK, "the statistics of a tile fit one entry per thread");
+
+__device__ __forceinline__ float wsum(float v) {
+#pragma unroll
+  for (int o = CA_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, CA_WAVE);
+  return v;
+}
+__device__ __forceinline__ float wmax(float v) {
+#pragma unroll
+  for (int o = CA_WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, CA_WAVE));
+  return v;
+}
+
+// ---------------------------------------------------------------- window / candidate operands
+// grid (B S): a1[r] = [xd[b, s-1], xd[b, s], xd[b, s+1], cd[b]] (circular shift, user_encoder.py:128-144), a2[r] = [cd[b], xd[b, s]]
+// (:149-151), cd[b] = dropout1(c[b]) (:122), xd = dropout2(x) (:123).  c is read by its row stride (the cand[:, i, :] view).
+__global__ __launch_bounds__(CA_BLOCK) void pack_kernel(const float* __restrict__ x, const float* __restrict__ c, int64_t c_stride, int S, int D,
+                                                   Drop d1, Drop d2, float* __restrict__ a1, float* __restrict__ a2, float* __restrict__ cd) {
+  const int64_t r = blockIdx.x, b = r / S;
+  const int s = (int)(r - b * S);
+  const int sl = s == 0 ? S - 1 : s - 1, sr = s == S - 1 ? 0 : s + 1;
+  const size_t xb = (size_t)b * S * D;
+  for (int d = threadIdx.x; d < D; d += CA_BLOCK) {
+    const size_t il = xb + (size_t)sl * D + d, im = xb + (size_t)s * D + d, ir = xb + (size_t)sr * D + d;
+    const float vl = d2.apply(x[il], il), vm = d2.apply(x[im], im), vr = d2.apply(x[ir], ir);
+    const float cv = d1.apply(c[b * c_stride + d], (uint64_t)b * D + d);
+    float* p1 = a1 + (size_t)r * 4 * D;
+    p1[d] = vl; p1[D + d] = vm; p1[2 * D + d] = vr; p1[3 * D + d] = cv;
+    float* p2 = a2 + (size_t)r * 2 * D;
+    p2[d] = cv; p2[D + d] = vm;
+    if (s == 0) cd[(size_t)b * D + d] = cv;
+  }
+}
+
+// ---------------------------------------------------------------- nn.Linear with leading dimensions
+// y[r, o] = act(b[o] + rowadd[r / S, o] + sum_k x[r, k] W[o, k]); x [R, K] contiguous, W rows ldw apart, y rows ldy apart (a column
+// range of a wider buffer).  grid (ceil(R / CA_ROWS), ceil(O / CA_OT)): a workgroup owns CA_ROWS rows x CA_OT output features and walks K
+// in steps of CA_KS, the x rows and the weight tile staged in LDS by whole coalesced rows (the tile padded by one float against bank
+// conflicts); thread = (output feature, wave): each wave takes a quarter of every step on its own chain, and the four partial sums
+// meet in LDS and are added pairwise, in a fixed order.
+// TANH with `deriv` [R, O]: also tanh' = 4 e / (1 + e)^2, e = exp(-2 |pre|), taken from the pre-activation while it is in a register.
+// 1 - y^2 from the rounded y loses 2 y^2 / (1 - y^2) of y's relative error — 18 x at y = 0.95 — and the bias gradients of the dense
+// attention sum hundreds of such terms that cancel.
+template <bool TANH>
+__global__ __launch_bounds__(CA_BLOCK) void lin_kernel(const float* __restrict__ x, const float* __restrict__ W, int ldw, const float* __restrict__ b,
+                                                  const float* __restrict__ rowadd, int S, int64_t R, int K, int O, float* __restrict__ y, int ldy,
+                                                  float* __restrict__ deriv) {
+  __shared__ float xs[CA_ROWS][CA_KS];
+  __shared__ float ws[CA_OT][CA_KS + 1];
+  __shared__ float red[CA_WAVES][CA_ROWS][CA_OT];
+  const int64_t r0 = (int64_t)blockIdx.x * CA_ROWS;
+  const int nr = (int)min((int64_t)CA_ROWS, R - r0);
+  const int o0 = blockIdx.y * CA_OT, oc = threadIdx.x % CA_OT, kq = threadIdx.x / CA_OT;
+  float acc[CA_ROWS];
+#pragma unroll
+  for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = 0.f;
+  for (int k0 = 0; k0 < K; k0 += CA_KS) {
+    const int kc = min(CA_KS, K - k0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < CA_ROWS * CA_KS; i += CA_BLOCK) {
+      const int rr = i / CA_KS, k = i - rr * CA_KS;
+      xs[rr][k] = (rr < nr && k < kc) ? x[(size_t)(r0 + rr) * K + k0 + k] : 0.f;
+    }
+    for (int i = threadIdx.x; i < CA_OT * CA_KS; i += CA_BLOCK) {
+      const int oo = i / CA_KS, k = i - oo * CA_KS;
+      ws[oo][k] = (o0 + oo < O && k < kc) ? W[(size_t)(o0 + oo) * ldw + k0 + k] : 0.f;      // past O or K: zeros, no branch below
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int k = kq * (CA_KS / CA_WAVES); k < (kq + 1) * (CA_KS / CA_WAVES); ++k) {
+      const float wv = ws[oc][k];
+#pragma unroll
+      for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = fmaf(xs[rr][k], wv, acc[rr]);
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < CA_ROWS; ++rr) red[kq][rr][oc] = acc[rr];
+  __syncthreads();
+  const int o = o0 + oc;
+  if (kq == 0 && o < O) {
+    const float bv = b ? b[o] : 0.f;
+#pragma unroll
+    for (int rr = 0; rr < CA_ROWS; ++rr)
+      if (rr < nr) {
+        float v = ((red[0][rr][oc] + red[1][rr][oc]) + (red[2][rr][oc] + red[3][rr][oc])) + bv;
+        if (rowadd) v += rowadd[(size_t)((r0 + rr) / S) * O + o];
+        y[(size_t)(r0 + rr) * ldy + o] = TANH ? tanhf(v) : v;
+        if (TANH && deriv) {
+          const float e = expf(-2.0f * fabsf(v)), den = 1.0f + e;
+          deriv[(size_t)(r0 + rr) * O + o] = 4.0f * e / (den * den);
+        }
+      }
+  }
+}
+// dx[r, k] = (add[r, k] + sum_o dy[r, o] W[o, k]) * mul[r, k]: dy rows ldy apart, W rows ldw apart, dx / add / mul [R, K]
+// contiguous (add, mul may be NULL); `add` may be dx itself (each element is read and written by one thread).
+// grid (ceil(R / CA_ROWS), ceil(K / CA_BLOCK)): thread = input feature (the weight rows are read coalesced), o ascending on one chain.
+__global__ __launch_bounds__(CA_BLOCK) void lin_dx_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ W, int ldw, int64_t R, int K,
+                                                     int O, const float* add, const float* __restrict__ mul, float* dx) {
+  __shared__ float ds[CA_ROWS][CA_OC];
+  const int64_t r0 = (int64_t)blockIdx.x * CA_ROWS;
+  const int nr = (int)min((int64_t)CA_ROWS, R - r0);
+  const int k = blockIdx.y * CA_BLOCK + threadIdx.x;
+  float acc[CA_ROWS];
+#pragma unroll
+  for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = 0.f;
+  for (int o0 = 0; o0 < O; o0 += CA_OC) {
+    const int no = min(CA_OC, O - o0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < CA_ROWS * no; i += CA_BLOCK) {
+      const int rr = i / no, o = i - rr * no;
+      ds[rr][o] = rr < nr ? dy[(size_t)(r0 + rr) * ldy + o0 + o] : 0.f;
+    }
+    __syncthreads();
+    if (k < K)
+      for (int o = 0; o < no; ++o) {
+        const float w = W[(size_t)(o0 + o) * ldw + k];
+#pragma unroll
+        for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = fmaf(ds[rr][o], w, acc[rr]);
+      }
+  }
+  if (k < K) {
+#pragma unroll
+    for (int rr = 0; rr < CA_ROWS; ++rr)
+      if (rr < nr) {
+        const size_t at = (size_t)(r0 + rr) * K + k;
+        float v = acc[rr] + (add ? add[at] : 0.f);
+        if (mul) v *= mul[at];
+        dx[at] = v;
+      }
+  }
+}
+// dW[o, k] = sum_r dy[r, o] x[r, k], dW rows ldo apart.  grid (ceil(K / 256), O, G): group g sums its rows on four chains into
+// part[g][o][k] (straight into dW when G == 1); wgrad_reduce_kernel adds the G partial sums in ascending g.
+__global__ __launch_bounds__(CA_BLOCK) void wgrad_rows_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ x, int64_t R, int K, int O,
+                                                         int64_t chunk, float* __restrict__ out, int ldo, int64_t gstride) {
+  const int k = blockIdx.x * CA_BLOCK + threadIdx.x, o = blockIdx.y;
+  if (k >= K) return;
+  const int64_t r0 = (int64_t)blockIdx.z * chunk, r1 = min(R, r0 + chunk);
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  int64_t r = r0;
+  for (; r + 3 < r1; r += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = fmaf(dy[(r + u) * ldy + o], x[(r + u) * K + k], a[u]);
+  }
+  for (; r < r1; ++r) a[0] = fmaf(dy[r * ldy + o], x[r * K + k], a[0]);
+  out[(size_t)blockIdx.z * gstride + (size_t)o * ldo + k] = (a[0] + a[1]) + (a[2] + a[3]);
+}
+__global__ __launch_bounds__(CA_BLOCK) void wgrad_reduce_kernel(const float* __restrict__ part, int K, int O, int G, float* __restrict__ dW, int ldo) {
+  const int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x, n = (int64_t)O * K;
+  if (i >= n) return;
+  float s = part[i];
+  for (int g = 1; g < G; ++g) s += part[(size_t)g * n + i];
+  const int64_t o = i / K;
+  dW[o * ldo + (i - o * K)] = s;
+}
+// db[o] = sum_r dy[r, o] (train_small.hip's colsum_small_kernel with a leading dimension)
+__global__ __launch_bounds__(CS_COLS * CS_GROUPS) void colsum_kernel(const float* __restrict__ dy, int ldy, int64_t R, int O, float* __restrict__ db) {
+  __shared__ float red[CS_GROUPS][CS_COLS];
+  const int col = threadIdx.x % CS_COLS, g = threadIdx.x / CS_COLS;
+  const int o = blockIdx.x * CS_COLS + col;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (o < O) {
+    int64_t r = g;
+    for (; r + 3 * CS_GROUPS < R; r += 4 * CS_GROUPS) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s[u] += dy[(r + u * CS_GROUPS) * ldy + o];
+    }
+    for (; r < R; r += CS_GROUPS) s[0] += dy[r * ldy + o];
+  }
+  red[g][col] = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  if (g == 0 && o < O) {
+    float t[CS_GROUPS];
+#pragma unroll
+    for (int i = 0; i < CS_GROUPS; ++i) t[i] = red[i][col];
+#pragma unroll
+    for (int w = CS_GROUPS / 2; w > 0; w >>= 1) {
+#pragma unroll
+      for (int i = 0; i < w; ++i) t[i] += t[i + w];
+    }
+    db[o] = t[0];
+  }
+}
+
+int launch_lin(bool tanh_act, const float* x, const float* W, int ldw, const float* b, const float* rowadd, int S, int64_t R, int K, int O, float* y,
+               int ldy, hipStream_t s, float* deriv = nullptr) {
+  const dim3 g((unsigned)((R + CA_ROWS - 1) / CA_ROWS), (unsigned)((O + CA_OT - 1) / CA_OT));
+  if (tanh_act) hipLaunchKernelGGL(lin_kernel<true>, g, dim3(CA_BLOCK), 0, s, x, W, ldw, b, rowadd, S, R, K, O, y, ldy, deriv);
+  else hipLaunchKernelGGL(lin_kernel<false>, g, dim3(CA_BLOCK), 0, s, x, W, ldw, b, rowadd, S, R, K, O, y, ldy, deriv);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+int launch_dx(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, const float* add, const float* mul, float* dx, hipStream_t s) {
+  hipLaunchKernelGGL(lin_dx_kernel, dim3((unsigned)((R + CA_ROWS - 1) / CA_ROWS), (unsigned)((K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, dy, ldy, W, ldw, R, K, O, add, mul, dx);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+int wgrad_groups(int64_t R) { return (int)std::max<int64_t>(1, std::min<int64_t>(WG_MAX_GROUPS, R / WG_ROWS)); }
+// R >= 1; part holds wgrad_groups(R) * O * K floats
+int launch_wgrad(const float* dy, int ldy, const float* x, int64_t R, int K, int O, float* part, float* dW, int ldo, hipStream_t s) {
+  const int G = wgrad_groups(R);
+  const int64_t chunk = (R + G - 1) / G;
+  const dim3 g((unsigned)((K + CA_BLOCK - 1) / CA_BLOCK), (unsigned)O, (unsigned)G);
+  if (G == 1) hipLaunchKernelGGL(wgrad_rows_kernel, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, R, K, O, chunk, dW, ldo, (int64_t)0);
+  else hipLaunchKernelGGL(wgrad_rows_kernel, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, R, K, O, chunk, part, K, (int64_t)O * K);
+  MANNER_LAUNCH_CHECK();
+  if (G > 1) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((int64_t)O * K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, part, K, O, G, dW, ldo);
+    MANNER_LAUNCH_CHECK();
+  }
+  return MANNER_HIP_OK;
+}
+int launch_colsum(const float* dy, int ldy, int64_t R, int O, float* db, hipStream_t s) {
+  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((O + CS_COLS - 1) / CS_COLS)), dim3(CS_COLS * CS_GROUPS), 0, s, dy, ldy, R, O, db);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+// ---------------------------------------------------------------- axis-0 attention at any head dim
+// qkv [N, E, 3D] (q | k | v), attention along the N axis for each (slot e, head) pair; dh = D / heads is a run-time value under the
+// compile-time register width DHP.  The arithmetic is that of train_small.hip's axis0_fwd_kernel / axis0_bwd_*: q scaled first, online
+// softmax over the keys in ascending order.  Threads are filled at small N: a workgroup takes P pairs, thread = (pair, row), and the
+// K / V rows (backward-kv: the Q / d out rows) of all its pairs sit in LDS (A0Plan: P * N * dh <= CA_LDS floats per operand).  A pair
+// that does not fit, or N > 256, runs alone in its workgroups with the other side streamed in tiles of CA_KT rows.
+struct A0Plan { int P, KT, RQ; };          // pairs per workgroup, other-side rows per tile, own rows per workgroup
+A0Plan a0_plan(int64_t N, int dh) {
+  if (N <= CA_BLOCK && N * dh <= CA_LDS) {
+    const int n = (int)N;
+    return A0Plan{std::min(CA_BLOCK / n, CA_LDS / (n * dh)), n, n};
+  }
+  return A0Plan{1, CA_KT, CA_BLOCK};
+}
+struct A0Thread {
+  bool act;
+  int pl, pair, e, hh;
+  int64_t n;
+};
+__device__ __forceinline__ A0Thread a0_thread(const A0Plan& pl, int64_t N, int E, int heads) {
+  A0Thread t;
+  t.pl = threadIdx.x / pl.RQ;
+  t.n = (int64_t)blockIdx.y * pl.RQ + (threadIdx.x - t.pl * pl.RQ);
+  t.pair = blockIdx.x * pl.P + t.pl;
+  t.act = t.pl < pl.P && t.pair < E * heads && t.n < N;
+  if (!t.act) { t.pair = 0; t.n = 0; }
+  t.e = t.pair / heads;
+  t.hh = t.pair - t.e * heads;
+  return t;
+}
+// stages the rows [t0, t0 + cnt) of the workgroup's pairs: a[(pp * KT + j) * dh + d] = src_a[...], likewise b
+template <typename FA, typename FB>
+__device__ __forceinline__ void a0_stage(const A0Plan& pl, int cnt, int dh, int E, int heads, float* a, float* b, FA fa, FB fb) {
+  const int per = cnt * dh;
+  for (int i = threadIdx.x; i < pl.P * per; i += CA_BLOCK) {
+    const int pp = i / per, rem = i - pp * per, j = rem / dh, d = rem - j * dh;
+    const int gp = blockIdx.x * pl.P + pp;
+    const bool ok = gp < E * heads;
+    const int e = ok ? gp / heads : 0, hh = ok ? gp - e * heads : 0;
+    a[(pp * pl.KT + j) * dh + d] = ok ? fa(j, e, hh, d) : 0.f;
+    b[(pp * pl.KT + j) * dh + d] = ok ? fb(j, e, hh, d) : 0.f;
+  }
+}
+
+template <int DHP>
+__global__ __launch_bounds__(CA_BLOCK) void a0any_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ stats, int64_t N,
+                                                        int E, int D, int heads, int dh, A0Plan pl) {
+  __shared__ float ks[CA_LDS], vs[CA_LDS];
+  const A0Thread t = a0_thread(pl, N, E, heads);
+  const float scale = 1.0f / sqrtf((float)dh);
+  const size_t ld = (size_t)E * 3 * D;
+  const float* base = qkv + (size_t)t.e * 3 * D + t.hh * dh;
+  float q[DHP], o[DHP];
+#pragma unroll
+  for (int d = 0; d < DHP; ++d) { q[d] = (t.act && d < dh) ? base[t.n * ld + d] * scale : 0.f; o[d] = 0.f; }
+  float mx = -INFINITY, sum = 0.f;
+  for (int64_t t0 = 0; t0 < N; t0 += pl.KT) {
+    const int cnt = (int)min((int64_t)pl.KT, N - t0);
+    __syncthreads();
+    a0_stage(pl, cnt, dh, E, heads, ks, vs,
+             [&](int j, int e, int hh, int d) { return qkv[(t0 + j) * ld + (size_t)e * 3 * D + D + hh * dh + d]; },
+             [&](int j, int e, int hh, int d) { return qkv[(t0 + j) * ld + (size_t)e * 3 * D + 2 * D + hh * dh + d]; });
+    __syncthreads();
+    if (t.act)
+      for (int j = 0; j < cnt; ++j) {
+        const float* kp = ks + (t.pl * pl.KT + j) * dh;
+        const float* vp = vs + (t.pl * pl.KT + j) * dh;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) s = fmaf(q[d], kp[d], s);
+        if (s > mx) {
+          const float f = expf(mx - s);
+          sum *= f;
+#pragma unroll
+          for (int d = 0; d < DHP; ++d) o[d] *= f;
+          mx = s;
+        }
+        const float p = expf(s - mx);
+        sum += p;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) o[d] = fmaf(p, vp[d], o[d]);
+      }
+  }
+  if (t.act) {
+    const float inv = 1.0f / sum;
+    float* dst = out + (size_t)t.n * E * D + (size_t)t.e * D + t.hh * dh;
+#pragma unroll
+    for (int d = 0; d < DHP; ++d)
+      if (d < dh) dst[d] = o[d] * inv;
+    if (stats) {
+      float* st = stats + ((size_t)t.n * E * heads + t.pair) * 3;
+      st[0] = mx; st[1] = sum;
+    }
+  }
+}
+// thread = query row: D_i = d out_i . out_i (= sum_j dP_ij P_ij), dq_i = sum_j P_ij (dP_ij - D_i) k_j / sqrt(dh); stats gets D_i
+template <int DHP>
+__global__ __launch_bounds__(CA_BLOCK) void a0any_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ att, const float* __restrict__ datt,
+                                                          float* __restrict__ dqkv, float* __restrict__ stats, int64_t N, int E, int D, int heads,
+                                                          int dh, A0Plan pl) {
+  __shared__ float ks[CA_LDS], vs[CA_LDS];
+  const A0Thread t = a0_thread(pl, N, E, heads);
+  const float scale = 1.0f / sqrtf((float)dh);
+  const size_t ld = (size_t)E * 3 * D;
+  const float* base = qkv + (size_t)t.e * 3 * D + t.hh * dh;
+  const size_t oat = (size_t)t.n * E * D + (size_t)t.e * D + t.hh * dh;
+  float q[DHP], go[DHP], dq[DHP];
+  float Dn = 0.f;
+#pragma unroll
+  for (int d = 0; d < DHP; ++d) {
+    const bool on = t.act && d < dh;
+    q[d] = on ? base[t.n * ld + d] * scale : 0.f;
+    go[d] = on ? datt[oat + d] : 0.f;
+    if (on) Dn = fmaf(go[d], att[oat + d], Dn);
+    dq[d] = 0.f;
+  }
+  float* st = stats + ((size_t)t.n * E * heads + t.pair) * 3;
+  const float mx = t.act ? st[0] : 0.f, inv = t.act ? 1.0f / st[1] : 0.f;
+  for (int64_t t0 = 0; t0 < N; t0 += pl.KT) {
+    const int cnt = (int)min((int64_t)pl.KT, N - t0);
+    __syncthreads();
+    a0_stage(pl, cnt, dh, E, heads, ks, vs,
+             [&](int j, int e, int hh, int d) { return qkv[(t0 + j) * ld + (size_t)e * 3 * D + D + hh * dh + d]; },
+             [&](int j, int e, int hh, int d) { return qkv[(t0 + j) * ld + (size_t)e * 3 * D + 2 * D + hh * dh + d]; });
+    __syncthreads();
+    if (t.act)
+      for (int j = 0; j < cnt; ++j) {
+        const float* kp = ks + (t.pl * pl.KT + j) * dh;
+        const float* vp = vs + (t.pl * pl.KT + j) * dh;
+        float s = 0.f, gv = 0.f;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) { s = fmaf(q[d], kp[d], s); gv = fmaf(go[d], vp[d], gv); }
+        const float dsc = expf(s - mx) * inv * (gv - Dn) * scale;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) dq[d] = fmaf(dsc, kp[d], dq[d]);
+      }
+  }
+  if (t.act) {
+    float* dst = dqkv + t.n * ld + (size_t)t.e * 3 * D + t.hh * dh;
+#pragma unroll
+    for (int d = 0; d < DHP; ++d)
+      if (d < dh) dst[d] = dq[d];
+    st[2] = Dn;
+  }
+}
+// thread = key row: dk_j = sum_i dS_ij q_i (scaled), dv_j = sum_i P_ij d out_i, queries in ascending order
+template <int DHP>
+__global__ __launch_bounds__(CA_BLOCK) void a0any_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ datt, const float* __restrict__ stats,
+                                                           float* __restrict__ dqkv, int64_t N, int E, int D, int heads, int dh, A0Plan pl) {
+  __shared__ float qs[CA_LDS], gs[CA_LDS];
+  __shared__ float sm[CA_BLOCK], sl[CA_BLOCK], sd[CA_BLOCK];
+  const A0Thread t = a0_thread(pl, N, E, heads);
+  const float scale = 1.0f / sqrtf((float)dh);
+  const size_t ld = (size_t)E * 3 * D;
+  const float* base = qkv + (size_t)t.e * 3 * D + t.hh * dh;
+  float k[DHP], v[DHP], dk[DHP], dv[DHP];
+#pragma unroll
+  for (int d = 0; d < DHP; ++d) {
+    const bool on = t.act && d < dh;
+    k[d] = on ? base[t.n * ld + D + d] : 0.f;
+    v[d] = on ? base[t.n * ld + 2 * D + d] : 0.f;
+    dk[d] = dv[d] = 0.f;
+  }
+  for (int64_t t0 = 0; t0 < N; t0 += pl.KT) {
+    const int cnt = (int)min((int64_t)pl.KT, N - t0);
+    __syncthreads();
+    a0_stage(pl, cnt, dh, E, heads, qs, gs,
+             [&](int j, int e, int hh, int d) { return qkv[(t0 + j) * ld + (size_t)e * 3 * D + hh * dh + d] * scale; },
+             [&](int j, int e, int hh, int d) { return datt[(size_t)(t0 + j) * E * D + (size_t)e * D + hh * dh + d]; });
+    for (int i = threadIdx.x; i < pl.P * cnt; i += CA_BLOCK) {      // P * cnt <= 256 (resident: P * N <= 256; tiled: CA_KT)
+      const int pp = i / cnt, j = i - pp * cnt;
+      const int gp = blockIdx.x * pl.P + pp;
+      const float* st = stats + ((size_t)(t0 + j) * E * heads + (gp < E * heads ? gp : 0)) * 3;
+      sm[pp * pl.KT + j] = st[0]; sl[pp * pl.KT + j] = 1.f / st[1]; sd[pp * pl.KT + j] = st[2];
+    }
+    __syncthreads();
+    if (t.act)
+      for (int i = 0; i < cnt; ++i) {
+        const int at = t.pl * pl.KT + i;
+        const float* qp = qs + at * dh;
+        const float* gp = gs + at * dh;
+        float s = 0.f, gv = 0.f;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) { s = fmaf(qp[d], k[d], s); gv = fmaf(gp[d], v[d], gv); }
+        const float p = expf(s - sm[at]) * sl[at];
+        const float dsc = p * (gv - sd[at]);               // qs carries the 1/sqrt(dh)
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) { dk[d] = fmaf(dsc, qp[d], dk[d]); dv[d] = fmaf(p, gp[d], dv[d]); }
+      }
+  }
+  if (t.act) {
+    float* dst = dqkv + t.n * ld + (size_t)t.e * 3 * D + t.hh * dh;
+#pragma unroll
+    for (int d = 0; d < DHP; ++d)
+      if (d < dh) { dst[D + d] = dk[d]; dst[2 * D + d] = dv[d]; }
+  }
+}
+
+int a0any_check(const char* who, int64_t L0, int64_t B1, int E, int heads) {
+  if (L0 < 0 || B1 < 0 || E <= 0 || heads <= 0 || E % heads)
+    return fail(MANNER_HIP_E_INVALID, "%s: bad shape L0=%lld B1=%lld E=%d heads=%d", who, (long long)L0, (long long)B1, E, heads);
+  if (E / heads > CA_MAX_DH) return fail(MANNER_HIP_E_INVALID, "%s: head_dim %d unsupported (1 <= head_dim <= %d)", who, E / heads, CA_MAX_DH);
+  if (B1 * heads > 0x7fffffffll || (L0 + CA_BLOCK - 1) / CA_BLOCK > 65535) return fail(MANNER_HIP_E_INVALID, "%s: L0 or B1 exceeds the grid", who);
+  return MANNER_HIP_OK;
+}
+#define MANNER_A0ANY_DISPATCH(DH_, CALL) \
+  do {                                   \
+    if (DH_ <= 8) CALL(8);               \
+    else if (DH_ <= 16) CALL(16);        \
+    else if (DH_ <= 32) CALL(32);        \
+    else CALL(64);                       \
+  } while (0)
+
+int launch_a0any_fwd(const float* qkv, float* out, float* stats, int64_t N, int64_t E, int D, int heads, hipStream_t s) {
+  const int dh = D / heads;
+  const A0Plan pl = a0_plan(N, dh);
+  const dim3 g((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_fwd_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qkv, out, stats, N, (int)E, D, heads, dh, pl)
+  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+#undef MANNER_A0
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+int launch_a0any_bwd_q(const float* qkv, const float* att, const float* datt, float* dqkv, float* stats, int64_t N, int64_t E, int D, int heads,
+                       hipStream_t s) {
+  const int dh = D / heads;
+  const A0Plan pl = a0_plan(N, dh);
+  const dim3 g((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_bwd_q_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qkv, att, datt, dqkv, stats, N, (int)E, D, heads, dh, pl)
+  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+#undef MANNER_A0
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+int launch_a0any_bwd_kv(const float* qkv, const float* datt, const float* stats, float* dqkv, int64_t N, int64_t E, int D, int heads, hipStream_t s) {
+  const int dh = D / heads;
+  const A0Plan pl = a0_plan(N, dh);
+  const dim3 g((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_bwd_kv_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qkv, datt, stats, dqkv, N, (int)E, D, heads, dh, pl)
+  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+#undef MANNER_A0
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+// ---------------------------------------------------------------- dense-attention tail
+// grid (ceil(R / CA_ROWS)), one wave per row, two rows each: score[r] = t2[r, :] . wc + bc (attention.py:139) and
+// g[r] = cd[b, :] . all[r, :] — the final dot product (user_encoder.py:174-176) taken inside the sum: out[b] = sum_s p[s] g[b, s].
+__global__ __launch_bounds__(CA_BLOCK) void score_kernel(const float* __restrict__ t2, const float* __restrict__ wc, const float* __restrict__ bc,
+                                                    const float* __restrict__ all, const float* __restrict__ cd, int64_t R, int S, int H2, int U,
+                                                    float* __restrict__ score, float* __restrict__ g) {
+  const int wave = threadIdx.x / CA_WAVE, lane = threadIdx.x % CA_WAVE;
+  for (int rr = wave; rr < CA_ROWS; rr += CA_WAVES) {
+    const int64_t r = (int64_t)blockIdx.x * CA_ROWS + rr;
+    if (r >= R) break;                               // wave-uniform
+    const float* cb = cd + (size_t)(r / S) * U;
+    float a = 0.f, d = 0.f;
+    for (int j = lane; j < H2; j += CA_WAVE) a = fmaf(t2[r * H2 + j], wc[j], a);
+    for (int j = lane; j < U; j += CA_WAVE) d = fmaf(cb[j], all[r * U + j], d);
+    a = wsum(a); d = wsum(d);
+    if (lane == 0) { score[r] = a + bc[0]; g[r] = d; }
+  }
+}
+// grid (ceil(B / 4)), one wave per user: p = softmax over ALL S slots (user_encoder.py:172, no mask), out[b] = sum_s p[s] g[b, s].
+// With dout: ds[r] = p (dout g - sum p dout g) (the score's gradient), wq[r] = dout p (the weight of cd[b] in d all[r]); the backward
+// rebuilds p from the saved scores (S exps per user) instead of reading it back.  This is the one kernel with fewer than B x row-tiles
+// workgroups: what is left per user after score_kernel are S <= 256 scalars, CA_MAX_S / CA_WAVE per lane of one wave.
+__global__ __launch_bounds__(CA_BLOCK) void user_kernel(const float* __restrict__ score, const float* __restrict__ g, int64_t B, int S,
+                                                   float* __restrict__ out, const float* __restrict__ dout,
+                                                   float* __restrict__ ds, float* __restrict__ wq) {
+  const int lane = threadIdx.x % CA_WAVE;
+  const int64_t b = (int64_t)blockIdx.x * CA_WAVES + (threadIdx.x / CA_WAVE);
+  if (b >= B) return;
+  float l[CA_MAX_S / CA_WAVE], gv[CA_MAX_S / CA_WAVE], m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < CA_MAX_S / CA_WAVE; ++j) {
+    const int s = lane + CA_WAVE * j;
+    l[j] = s < S ? score[b * S + s] : -INFINITY;
+    gv[j] = s < S ? g[b * S + s] : 0.f;
+    m = fmaxf(m, l[j]);
+  }
+  m = wmax(m);
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < CA_MAX_S / CA_WAVE; ++j) {
+    l[j] = lane + CA_WAVE * j < S ? expf(l[j] - m) : 0.f;
+    sum += l[j];
+  }
+  sum = wsum(sum);
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < CA_MAX_S / CA_WAVE; ++j) {
+    l[j] /= sum;
+    acc = fmaf(l[j], gv[j], acc);
+  }
+  acc = wsum(acc);
+  if (!dout) {
+    if (lane == 0) out[b] = acc;
+    return;
+  }
+  const float go = dout[b];
+#pragma unroll
+  for (int j = 0; j < CA_MAX_S / CA_WAVE; ++j) {
+    const int s = lane + CA_WAVE * j;
+    if (s < S) {
+      ds[b * S + s] = l[j] * (go * (gv[j] - acc));            // the difference first: exactly zero at S = 1, as in torch
+      wq[b * S + s] = go * l[j];
+    }
+  }
+}
+// grid (ceil(R / CA_ROWS)): dt2[r, j] = ds[r] wc[j] tanh'[r, j] (d2, saved by the forward), dall[r, d] = wq[r] cd[b, d]
+__global__ __launch_bounds__(CA_BLOCK) void tail_rows_kernel(const float* __restrict__ ds, const float* __restrict__ wq, const float* __restrict__ wc,
+                                                        const float* __restrict__ d2, const float* __restrict__ cd, int64_t R, int S, int H2, int U,
+                                                        float* __restrict__ dt2, float* __restrict__ dall) {
+  for (int rr = 0; rr < CA_ROWS; ++rr) {
+    const int64_t r = (int64_t)blockIdx.x * CA_ROWS + rr;
+    if (r >= R) break;
+    const float dsr = ds[r], wr = wq[r];
+    const float* cb = cd + (size_t)(r / S) * U;
+    for (int j = threadIdx.x; j < H2; j += CA_BLOCK) dt2[r * H2 + j] = dsr * wc[j] * d2[r * H2 + j];
+    for (int d = threadIdx.x; d < U; d += CA_BLOCK) dall[r * U + d] = wr * cb[d];
+  }
+}
+// out[b, j] = add[b, j] + sum_s w[b, s] x[b, s, off + j] (w == NULL: 1), s ascending on two chains; x rows ldx apart.
+// grid (B, ceil(cols / 256)).  With `drop`: out = dropout-mask(out) by element index b * cols + j (the candidate's gradient).
+__global__ __launch_bounds__(CA_BLOCK) void segsum_kernel(const float* __restrict__ w, const float* __restrict__ x, int ldx, int off, const float* __restrict__ x2,
+                                                     int ldx2, const float* __restrict__ add, int S, int cols, Drop drop, bool dropped,
+                                                     float* __restrict__ out) {
+  const int64_t b = blockIdx.x;
+  const int j = blockIdx.y * CA_BLOCK + threadIdx.x;
+  if (j >= cols) return;
+  float a0 = 0.f, a1 = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const size_t r = (size_t)b * S + s;
+    float v = x[r * ldx + off + j];
+    if (x2) v += x2[r * ldx2 + j];
+    if (w) v *= w[r];
+    if (s & 1) a1 += v; else a0 += v;
+  }
+  float v = (a0 + a1) + (add ? add[(size_t)b * cols + j] : 0.f);
+  if (dropped) v = drop.apply(v, (uint64_t)b * cols + j);
+  out[(size_t)b * cols + j] = v;
+}
+// grid (B S): d x[b, s] = mask2 (dA1[b, s+1][0:D] + dA1[b, s][D:2D] + dA1[b, s-1][2D:3D] + dA2[b, s][D:2D]) — a gather of the three
+// windows that read x[b, s] (circular), not a scatter
+__global__ __launch_bounds__(CA_BLOCK) void window_dx_kernel(const float* __restrict__ da1, const float* __restrict__ da2, int S, int D, Drop d2,
+                                                        float* __restrict__ dx) {
+  const int64_t r = blockIdx.x, b = r / S;
+  const int s = (int)(r - b * S);
+  const int sl = s == 0 ? S - 1 : s - 1, sr = s == S - 1 ? 0 : s + 1;
+  const size_t rb = (size_t)b * S;
+  for (int d = threadIdx.x; d < D; d += CA_BLOCK) {
+    const float v = ((da1[(rb + sr) * 4 * D + d] + da1[(rb + s) * 4 * D + D + d]) + da1[(rb + sl) * 4 * D + 2 * D + d]) + da2[(rb + s) * 2 * D + D + d];
+    const size_t at = (rb + s) * D + d;
+    dx[at] = d2.apply(v, at);
+  }
+}
+__global__ __launch_bounds__(CA_BLOCK) void drop_inplace_kernel(float* x, int64_t n, Drop d) {
+  for (int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * CA_BLOCK) x[i] = d.apply(x[i], (uint64_t)i);
+}
+__global__ __launch_bounds__(CA_BLOCK) void relu_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * CA_BLOCK)
+    out[i] = g ? (x[i] > 0.f ? g[i] : 0.f) : fmaxf(x[i], 0.f);
+}
+__global__ __launch_bounds__(CA_BLOCK) void tanh_bwd_kernel(const float* __restrict__ y, const float* __restrict__ g, float* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * CA_BLOCK) out[i] = g[i] * (1.0f - y[i] * y[i]);
+}
+unsigned flat_grid(int64_t n) {
+  const int64_t blocks = (n + CA_BLOCK - 1) / CA_BLOCK;
+  return (unsigned)(blocks < CA_FLAT_GRID ? blocks : CA_FLAT_GRID);
+}
+
+// ---------------------------------------------------------------- CAUMUserEncoder
+struct Dims { int64_t B, S, R; int D, F, U, H1, H2, heads; };
+enum { P_W1, P_B1, P_W2, P_B2, P_WIN, P_BIN, P_WOUT, P_BOUT, P_W3, P_B3, P_WA, P_BA, P_WB, P_BB, P_WC, P_BC, P_COUNT };
+int caum_check(const char* who, int64_t B, int64_t S, int D, int F, int U, int H1, int H2, int heads, Dims& m) {
+  if (B < 0 || S < 1 || D < 1 || F < 1 || U < 1 || H1 < 1 || H2 < 1 || heads < 1 || U % heads)
+    return fail(MANNER_HIP_E_INVALID, "%s: bad shape B=%lld S=%lld D=%d F=%d U=%d H1=%d H2=%d heads=%d", who, (long long)B, (long long)S, D, F, U, H1,
+                H2, heads);
+  if (S > CA_MAX_S) return fail(MANNER_HIP_E_INVALID, "%s: S=%lld unsupported (S <= %d)", who, (long long)S, CA_MAX_S);
+  if (D > CA_MAX_W) return fail(MANNER_HIP_E_INVALID, "%s: D=%d unsupported (D <= %d)", who, D, CA_MAX_W);
+  if (F > CA_MAX_W) return fail(MANNER_HIP_E_INVALID, "%s: F=%d unsupported (F <= %d)", who, F, CA_MAX_W);
+  if (U > CA_MAX_W) return fail(MANNER_HIP_E_INVALID, "%s: U=%d unsupported (U <= %d)", who, U, CA_MAX_W);
+  if (H1 > CA_MAX_W) return fail(MANNER_HIP_E_INVALID, "%s: H1=%d unsupported (H1 <= %d)", who, H1, CA_MAX_W);
+  if (H2 > CA_MAX_W) return fail(MANNER_HIP_E_INVALID, "%s: H2=%d unsupported (H2 <= %d)", who, H2, CA_MAX_W);
+  if (D != U) return fail(MANNER_HIP_E_INVALID, "%s: news_vector_dim %d != user_vector_dim %d (the dense attention reads cat[all, candidate] as 2 x user_vector_dim)", who, D, U);
+  if (U / heads > CA_MAX_DH) return fail(MANNER_HIP_E_INVALID, "%s: head_dim %d unsupported (head_dim <= %d)", who, U / heads, CA_MAX_DH);
+  if (B * S > 0x7fffffffll || (B + CA_BLOCK - 1) / CA_BLOCK > 65535) return fail(MANNER_HIP_E_INVALID, "%s: B*S exceeds the grid", who);
+  m = Dims{B, S, B * S, D, F, U, H1, H2, heads};
+  return MANNER_HIP_OK;
+}
+struct Bump {
+  float* base;
+  size_t off = 0;
+  explicit Bump(void* p) : base(static_cast<float*>(p)) {}
+  float* take(size_t n) {
+    float* p = base ? base + off : nullptr;
+    off += (n + CA_ALIGN - 1) / CA_ALIGN * CA_ALIGN;
+    return p;
+  }
+};
+struct Saved { float *a1, *a2, *cd, *cat, *h2, *qkv, *att, *stats, *all, *ct, *t1, *t2, *d1, *d2, *score, *g; };
+void plan_saved(Bump& b, Saved& s, const Dims& m) {
+  const size_t R = (size_t)m.R, B = (size_t)m.B;
+  s.a1 = b.take(R * 4 * m.D);
+  s.a2 = b.take(R * 2 * m.D);
+  s.cd = b.take(B * m.D);
+  s.cat = b.take(R * (m.F + m.U));
+  s.h2 = b.take(R * m.U);
+  s.qkv = b.take(R * 3 * m.U);
+  s.att = b.take(R * m.U);
+  s.stats = b.take(R * m.heads * 3);
+  s.all = b.take(R * m.U);
+  s.ct = b.take(B * m.H1);
+  s.t1 = b.take(R * m.H1);
+  s.t2 = b.take(R * m.H2);
+  s.d1 = b.take(R * m.H1);                      // tanh' of the two dense-attention layers
+  s.d2 = b.take(R * m.H2);
+  s.score = b.take(R);
+  s.g = b.take(R);
+}
+struct Work { float *ds, *wq, *dt2, *dt1, *dall, *dct, *dcd, *dcat, *datt, *dqkv, *dh2, *da2, *da1, *part; };
+void plan_work(Bump& b, Work& w, const Dims& m) {
+  const size_t R = (size_t)m.R, B = (size_t)m.B;
+  w.ds = b.take(R);
+  w.wq = b.take(R);
+  w.dt2 = b.take(R * m.H2);
+  w.dt1 = b.take(R * m.H1);
+  w.dall = b.take(R * m.U);
+  w.dct = b.take(B * m.H1);
+  w.dcd = b.take(B * m.D);
+  w.dcat = b.take(R * (m.F + m.U));
+  w.datt = b.take(R * m.U);
+  w.dqkv = b.take(R * 3 * m.U);
+  w.dh2 = b.take(R * m.U);
+  w.da2 = b.take(R * 2 * m.D);
+  w.da1 = b.take(R * 4 * m.D);
+  const size_t ok = std::max({(size_t)m.F * 4 * m.D, (size_t)m.U * 2 * m.D, (size_t)3 * m.U * m.U, (size_t)m.U * (m.F + m.U), (size_t)m.H1 * m.U,
+                              (size_t)m.H2 * m.H1, (size_t)m.H2});
+  w.part = b.take((size_t)wgrad_groups(m.R) * ok);
+}
+
+}  // namespace
+}  // namespace manner
+
+using namespace manner;
+
+extern "C" {
+
+int manner_hip_relu(const float* x, float* out, int64_t n, manner_hip_stream_t stream) {
+  if (n == 0) return MANNER_HIP_OK;
+  if (n < 0 || !x || !out) return fail(MANNER_HIP_E_INVALID, "relu: bad argument");
+  hipLaunchKernelGGL(relu_kernel, dim3(flat_grid(n)), dim3(CA_BLOCK), 0, (hipStream_t)stream, x, (const float*)nullptr, out, n);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+int manner_hip_relu_backward(const float* x, const float* grad_out, float* grad_x, int64_t n, manner_hip_stream_t stream) {
+  if (n == 0) return MANNER_HIP_OK;
+  if (n < 0 || !x || !grad_out || !grad_x) return fail(MANNER_HIP_E_INVALID, "relu_backward: bad argument");
+  hipLaunchKernelGGL(relu_kernel, dim3(flat_grid(n)), dim3(CA_BLOCK), 0, (hipStream_t)stream, x, grad_out, grad_x, n);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+int manner_hip_linear_tanh(const float* x, const float* weight, const float* bias, int64_t R, int32_t K, int32_t O, float* y,
+                           manner_hip_stream_t stream) {
+  if (R < 0 || K <= 0 || O <= 0 || R > 0x7fffffffll || O > 65535 * CA_OT) return fail(MANNER_HIP_E_INVALID, "linear_tanh: bad shape");
+  if (R == 0) return MANNER_HIP_OK;
+  if (!x || !weight || !y) return fail(MANNER_HIP_E_INVALID, "linear_tanh: null pointer");
+  return launch_lin(true, x, weight, K, bias, nullptr, 1, R, K, O, y, O, (hipStream_t)stream);
+}
+
+int manner_hip_tanh_backward(const float* y, const float* grad_out, float* grad_pre, int64_t n, manner_hip_stream_t stream) {
+  if (n == 0) return MANNER_HIP_OK;
+  if (n < 0 || !y || !grad_out || !grad_pre) return fail(MANNER_HIP_E_INVALID, "tanh_backward: bad argument");
+  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(flat_grid(n)), dim3(CA_BLOCK), 0, (hipStream_t)stream, y, grad_out, grad_pre, n);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+int manner_hip_axis0_attention_any(const float* qkv, int64_t L0, int64_t B1, int32_t E, int32_t heads, float* out, float* stats,
+                                   manner_hip_stream_t stream) {
+  int rc;
+  if ((rc = a0any_check("axis0_attention_any", L0, B1, E, heads))) return rc;
+  if (L0 == 0 || B1 == 0) return MANNER_HIP_OK;
+  if (!qkv || !out) return fail(MANNER_HIP_E_INVALID, "axis0_attention_any: null pointer");
+  return launch_a0any_fwd(qkv, out, stats, L0, B1, E, heads, (hipStream_t)stream);
+}
+
+int manner_hip_axis0_attention_any_backward_q(const float* qkv, const float* out, const float* grad_out, int64_t L0, int64_t B1, int32_t E,
+                                              int32_t heads, float* grad_qkv, float* stats, manner_hip_stream_t stream) {
+  int rc;
+  if ((rc = a0any_check("axis0_attention_any_backward_q", L0, B1, E, heads))) return rc;
+  if (L0 == 0 || B1 == 0) return MANNER_HIP_OK;
+  if (!qkv || !out || !grad_out || !grad_qkv || !stats) return fail(MANNER_HIP_E_INVALID, "axis0_attention_any_backward_q: null pointer");
+  return launch_a0any_bwd_q(qkv, out, grad_out, grad_qkv, stats, L0, B1, E, heads, (hipStream_t)stream);
+}
+
+int manner_hip_axis0_attention_any_backward_kv(const float* qkv, const float* grad_out, const float* stats, int64_t L0, int64_t B1, int32_t E,
+                                               int32_t heads, float* grad_qkv, manner_hip_stream_t stream) {
+  int rc;
+  if ((rc = a0any_check("axis0_attention_any_backward_kv", L0, B1, E, heads))) return rc;
+  if (L0 == 0 || B1 == 0) return MANNER_HIP_OK;
+  if (!qkv || !grad_out || !grad_qkv || !stats) return fail(MANNER_HIP_E_INVALID, "axis0_attention_any_backward_kv: null pointer");
+  return launch_a0any_bwd_kv(qkv, grad_out, stats, grad_qkv, L0, B1, E, heads, (hipStream_t)stream);
+}
+
+size_t manner_hip_caum_user_saved_bytes(int64_t B, int64_t S, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads) {
+  if (B <= 0 || S <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
+  const Dims m{B, S, B * S, D, F, U, H1, H2, heads};
+  Bump b(nullptr);
+  Saved s;
+  plan_saved(b, s, m);
+  return b.off * sizeof(float) + 256;
+}
+
+int manner_hip_caum_user_forward(const float* x, const float* c, int64_t c_stride, const float* const* params, int64_t B, int64_t S, int32_t D,
+                                 int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads, float p, uint64_t seed, uint32_t site0, float* out,
+                                 void* saved, size_t saved_bytes, manner_hip_stream_t stream) {
+  int rc;
+  Dims m;
+  if ((rc = caum_check("caum_user", B, S, D, F, U, H1, H2, heads, m))) return rc;
+  if (!(p >= 0.f && p < 1.f)) return fail(MANNER_HIP_E_INVALID, "caum_user: p=%f outside [0, 1)", p);
+  if (B == 0) return MANNER_HIP_OK;
+  if (!x || !c || !params || !out || !saved) return fail(MANNER_HIP_E_INVALID, "caum_user: null pointer");
+  for (int i = 0; i < P_COUNT; ++i)
+    if (!params[i]) return fail(MANNER_HIP_E_INVALID, "caum_user: null parameter %d", i);
+  if (c_stride < D) return fail(MANNER_HIP_E_INVALID, "caum_user: candidate row stride %lld < D=%d", (long long)c_stride, D);
+  if (saved_bytes < manner_hip_caum_user_saved_bytes(B, S, D, F, U, H1, H2, heads)) return fail(MANNER_HIP_E_WORKSPACE, "caum_user: saved buffer too small");
+  hipStream_t s = (hipStream_t)stream;
+  Bump bump(saved);
+  Saved sv;
+  plan_saved(bump, sv, m);
+  const int64_t R = m.R;
+  const int FU = F + U, Si = (int)S;
+  const Drop d1 = make_drop(seed, site0, p), d2 = make_drop(seed, site0 + 1, p), d3 = make_drop(seed, site0 + 2, p);
+  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, x, c, c_stride, Si, D, d1, d2, sv.a1, sv.a2, sv.cd);
+  MANNER_LAUNCH_CHECK();
+  // candi-cnn into cat[:, :F]; candi-selfatt: Linear, in-projection, attention along B, out-projection into cat[:, F:]
+  if ((rc = launch_lin(false, sv.a1, params[P_W1], 4 * D, params[P_B1], nullptr, 1, R, 4 * D, F, sv.cat, FU, s))) return rc;
+  if ((rc = launch_lin(false, sv.a2, params[P_W2], 2 * D, params[P_B2], nullptr, 1, R, 2 * D, U, sv.h2, U, s))) return rc;
+  if ((rc = launch_lin(false, sv.h2, params[P_WIN], U, params[P_BIN], nullptr, 1, R, U, 3 * U, sv.qkv, 3 * U, s))) return rc;
+  if ((rc = launch_a0any_fwd(sv.qkv, sv.att, sv.stats, B, S, U, heads, s))) return rc;
+  if ((rc = launch_lin(false, sv.att, params[P_WOUT], U, params[P_BOUT], nullptr, 1, R, U, U, sv.cat + F, FU, s))) return rc;
+  if (p > 0.f) {
+    hipLaunchKernelGGL(drop_inplace_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, sv.cat, R * FU, d3);
+    MANNER_LAUNCH_CHECK();
+  }
+  if ((rc = launch_lin(false, sv.cat, params[P_W3], FU, params[P_B3], nullptr, 1, R, FU, U, sv.all, U, s))) return rc;
+  // candi-att: the candidate half of dense_att.linear once per user, then the two tanh layers over the rows
+  if ((rc = launch_lin(false, sv.cd, params[P_WA] + U, 2 * U, params[P_BA], nullptr, 1, B, D, H1, sv.ct, H1, s))) return rc;
+  if ((rc = launch_lin(true, sv.all, params[P_WA], 2 * U, nullptr, sv.ct, Si, R, U, H1, sv.t1, H1, s, sv.d1))) return rc;
+  if ((rc = launch_lin(true, sv.t1, params[P_WB], H1, params[P_BB], nullptr, 1, R, H1, H2, sv.t2, H2, s, sv.d2))) return rc;
+  hipLaunchKernelGGL(score_kernel, dim3((unsigned)((R + CA_ROWS - 1) / CA_ROWS)), dim3(CA_BLOCK), 0, s, sv.t2, params[P_WC], params[P_BC], sv.all, sv.cd, R,
+                     Si, H2, U, sv.score, sv.g);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(user_kernel, dim3((unsigned)((B + CA_WAVES - 1) / CA_WAVES)), dim3(CA_BLOCK), 0, s, sv.score, sv.g, B, Si, out, (const float*)nullptr,
+                     (float*)nullptr, (float*)nullptr);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+size_t manner_hip_caum_user_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads) {
+  if (B <= 0 || S <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
+  const Dims m{B, S, B * S, D, F, U, H1, H2, heads};
+  Bump b(nullptr);
+  Work w;
+  plan_work(b, w, m);
+  return b.off * sizeof(float) + 256;
+}
+
+int manner_hip_caum_user_backward(const float* const* params, const float* grad_out, int64_t B, int64_t S, int32_t D, int32_t F, int32_t U,
+                                  int32_t H1, int32_t H2, int32_t heads, float p, uint64_t seed, uint32_t site0, void* saved, size_t saved_bytes,
+                                  float* grad_x, float* grad_c, float* const* grads, void* workspace, size_t workspace_bytes,
+                                  manner_hip_stream_t stream) {
+  int rc;
+  Dims m;
+  if ((rc = caum_check("caum_user_backward", B, S, D, F, U, H1, H2, heads, m))) return rc;
+  if (!(p >= 0.f && p < 1.f)) return fail(MANNER_HIP_E_INVALID, "caum_user_backward: p=%f outside [0, 1)", p);
+  if (!params || !grads) return fail(MANNER_HIP_E_INVALID, "caum_user_backward: null pointer");
+  for (int i = 0; i < P_COUNT; ++i)
+    if (!params[i] || !grads[i]) return fail(MANNER_HIP_E_INVALID, "caum_user_backward: null parameter or gradient %d", i);
+  hipStream_t s = (hipStream_t)stream;
+  const int FU = F + U, Si = (int)S;
+  const size_t sizes[P_COUNT] = {(size_t)F * 4 * D, (size_t)F, (size_t)U * 2 * D, (size_t)U, (size_t)3 * U * U, (size_t)3 * U, (size_t)U * U, (size_t)U,
+                                 (size_t)U * FU, (size_t)U, (size_t)H1 * 2 * U, (size_t)H1, (size_t)H2 * H1, (size_t)H2, (size_t)H2, 1};
+  if (B == 0) {                                    // no user: the parameter gradients are sums over nothing
+    for (int i = 0; i < P_COUNT; ++i) MANNER_HIP_TRY(hipMemsetAsync(grads[i], 0, sizes[i] * sizeof(float), s));
+    return MANNER_HIP_OK;
+  }
+  if (!grad_out || !saved || !grad_x || !grad_c || !workspace) return fail(MANNER_HIP_E_INVALID, "caum_user_backward: null pointer");
+  if (saved_bytes < manner_hip_caum_user_saved_bytes(B, S, D, F, U, H1, H2, heads)) return fail(MANNER_HIP_E_WORKSPACE, "caum_user_backward: saved buffer too small");
+  if (workspace_bytes < manner_hip_caum_user_backward_workspace_bytes(B, S, D, F, U, H1, H2, heads))
+    return fail(MANNER_HIP_E_WORKSPACE, "caum_user_backward: workspace too small");
+  Bump bs(saved), bw(workspace);
+  Saved sv;
+  Work w;
+  plan_saved(bs, sv, m);
+  plan_work(bw, w, m);
+  const int64_t R = m.R;
+  const Drop d1 = make_drop(seed, site0, p), d2 = make_drop(seed, site0 + 1, p), d3 = make_drop(seed, site0 + 2, p);
+  const unsigned row_tiles = (unsigned)((R + CA_ROWS - 1) / CA_ROWS);
+  // the final dot, the weighted sum and the softmax: ds (d score), wq (the weight of cd[b] in d all)
+  hipLaunchKernelGGL(user_kernel, dim3((unsigned)((B + CA_WAVES - 1) / CA_WAVES)), dim3(CA_BLOCK), 0, s, sv.score, sv.g, B, Si, (float*)nullptr, grad_out,
+                     w.ds, w.wq);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tail_rows_kernel, dim3(row_tiles), dim3(CA_BLOCK), 0, s, w.ds, w.wq, params[P_WC], sv.d2, sv.cd, R, Si, H2, U, w.dt2, w.dall);
+  MANNER_LAUNCH_CHECK();
+  // dense_att.linear3: d wc = sum_r ds[r] t2[r]; d bc is zero in exact arithmetic (the softmax is shift-invariant)
+  if ((rc = launch_wgrad(w.ds, 1, sv.t2, R, H2, 1, w.part, grads[P_WC], H2, s))) return rc;
+  MANNER_HIP_TRY(hipMemsetAsync(grads[P_BC], 0, sizeof(float), s));
+  // dense_att.linear2
+  if ((rc = launch_wgrad(w.dt2, H2, sv.t1, R, H1, H2, w.part, grads[P_WB], H1, s))) return rc;
+  if ((rc = launch_colsum(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
+  if ((rc = launch_dx(w.dt2, H2, params[P_WB], H1, R, H1, H2, nullptr, sv.d1, w.dt1, s))) return rc;
+  // dense_att.linear: the history half over the rows, the candidate half over the users (d ct[b] = sum_s d t1[b, s])
+  if ((rc = launch_wgrad(w.dt1, H1, sv.all, R, U, H1, w.part, grads[P_WA], 2 * U, s))) return rc;
+  if ((rc = launch_colsum(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
+  if ((rc = launch_dx(w.dt1, H1, params[P_WA], 2 * U, R, U, H1, w.dall, nullptr, w.dall, s))) return rc;
+  hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((H1 + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.dt1, H1, 0,
+                     (const float*)nullptr, 0, (const float*)nullptr, Si, H1, d1, false, w.dct);
+  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_wgrad(w.dct, H1, sv.cd, B, D, H1, w.part, grads[P_WA] + U, 2 * U, s))) return rc;
+  // d cd[b] = dout[b] user[b] + d ct[b] Wa[:, U:] (the window and self-attention routes are added at the end)
+  hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, w.wq, sv.all, U, 0, (const float*)nullptr, 0,
+                     (const float*)nullptr, Si, U, d1, false, w.dcd);
+  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_dx(w.dct, H1, params[P_WA] + U, 2 * U, B, D, H1, w.dcd, nullptr, w.dcd, s))) return rc;
+  // linear3 and dropout3
+  if ((rc = launch_wgrad(w.dall, U, sv.cat, R, FU, U, w.part, grads[P_W3], FU, s))) return rc;
+  if ((rc = launch_colsum(w.dall, U, R, U, grads[P_B3], s))) return rc;
+  if ((rc = launch_dx(w.dall, U, params[P_W3], FU, R, FU, U, nullptr, nullptr, w.dcat, s))) return rc;
+  if (p > 0.f) {
+    hipLaunchKernelGGL(drop_inplace_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, w.dcat, R * FU, d3);
+    MANNER_LAUNCH_CHECK();
+  }
+  // candi-selfatt: out-projection, attention, in-projection, linear2
+  if ((rc = launch_wgrad(w.dcat + F, FU, sv.att, R, U, U, w.part, grads[P_WOUT], U, s))) return rc;
+  if ((rc = launch_colsum(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
+  if ((rc = launch_dx(w.dcat + F, FU, params[P_WOUT], U, R, U, U, nullptr, nullptr, w.datt, s))) return rc;
+  if ((rc = launch_a0any_bwd_q(sv.qkv, sv.att, w.datt, w.dqkv, sv.stats, B, S, U, heads, s))) return rc;
+  if ((rc = launch_a0any_bwd_kv(sv.qkv, w.datt, sv.stats, w.dqkv, B, S, U, heads, s))) return rc;
+  if ((rc = launch_wgrad(w.dqkv, 3 * U, sv.h2, R, U, 3 * U, w.part, grads[P_WIN], U, s))) return rc;
+  if ((rc = launch_colsum(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
+  // the K third of d in_proj_bias is zero in exact arithmetic (a shift of every key moves every logit of a row alike)
+  MANNER_HIP_TRY(hipMemsetAsync(grads[P_BIN] + U, 0, (size_t)U * sizeof(float), s));
+  if ((rc = launch_dx(w.dqkv, 3 * U, params[P_WIN], U, R, U, 3 * U, nullptr, nullptr, w.dh2, s))) return rc;
+  if ((rc = launch_wgrad(w.dh2, U, sv.a2, R, 2 * D, U, w.part, grads[P_W2], 2 * D, s))) return rc;
+  if ((rc = launch_colsum(w.dh2, U, R, U, grads[P_B2], s))) return rc;
+  if ((rc = launch_dx(w.dh2, U, params[P_W2], 2 * D, R, 2 * D, U, nullptr, nullptr, w.da2, s))) return rc;
+  // candi-cnn: linear1 from cat[:, :F]
+  if ((rc = launch_wgrad(w.dcat, FU, sv.a1, R, 4 * D, F, w.part, grads[P_W1], 4 * D, s))) return rc;
+  if ((rc = launch_colsum(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
+  if ((rc = launch_dx(w.dcat, FU, params[P_W1], 4 * D, R, 4 * D, F, nullptr, nullptr, w.da1, s))) return rc;
+  // d x: the three windows and the self-attention operand; d c: the sums over the slots, through dropout1
+  hipLaunchKernelGGL(window_dx_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, w.da1, w.da2, Si, D, d2, grad_x);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((D + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.da1, 4 * D, 3 * D, w.da2,
+                     2 * D, w.dcd, Si, D, d1, true, grad_c);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+}  // extern "C"

@@ -805,6 +805,104 @@ def bmm(a: Tensor, b: Tensor) -> Tensor:
     return out
 
 
+def axis0_attention_any(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
+    """The attention core of ``mha_axis0_any`` on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]; ``stats`` f32 [L0 * B1 * heads * 3]
+    receives the softmax statistics the backward reads."""
+    qkv = _dev(qkv, torch.float32, "qkv").contiguous()
+    l0, b1, e3 = qkv.shape
+    out = torch.empty((l0, b1, e3 // 3), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.load().manner_hip_axis0_attention_any(_ptr(qkv), l0, b1, e3 // 3, int(heads), _ptr(out), _ptr(stats), _stream()))
+    return out
+
+
+def mha_axis0_any(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    """``mha_axis0`` at ANY head dim 1..64 (CAUM ships 25 in its user encoder and 5 in its entity encoder): attention along AXIS 0 of
+    x [L0, B1, E], unmasked.  At L0 < 256 a workgroup takes several (slot, head) pairs, one thread per (pair, row)."""
+    x = _dev(x, torch.float32, "x").contiguous()
+    l0, b1, e = x.shape
+    if x.numel() == 0:
+        return torch.empty_like(x)
+    qkv = linear(x.reshape(l0 * b1, e), in_proj_w, in_proj_b).reshape(l0, b1, 3 * e)
+    att = axis0_attention_any(qkv, heads)
+    return linear(att.reshape(l0 * b1, e), out_proj_w, out_proj_b).reshape(l0, b1, e)
+
+
+CAUM_PARAMS = ("linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "multihead_attention.in_proj_weight",
+               "multihead_attention.in_proj_bias", "multihead_attention.out_proj.weight", "multihead_attention.out_proj.bias",
+               "linear3.weight", "linear3.bias", "dense_att.linear.weight", "dense_att.linear.bias", "dense_att.linear2.weight",
+               "dense_att.linear2.bias", "dense_att.linear3.weight", "dense_att.linear3.bias")
+CAUM_DROPOUT_SITE = 7     # dropout1 / 2 / 3 of CAUMUserEncoder draw at the sites 7, 8, 9 (2..6 are the news encoders')
+
+
+def _caum_operands(x: Tensor, c: Tensor, params: Sequence[Tensor], heads: int):
+    """Checked operands of the CAUM user-encoder entries: (x, c, params, dims); c keeps its row stride (the cand[:, i, :] view)."""
+    x = _dev(x, torch.float32, "clicked_news_vector").contiguous()
+    c = _dev(c, torch.float32, "cand_news_vector")
+    if x.dim() != 3 or c.dim() != 2 or c.shape[0] != x.shape[0] or c.shape[1] != x.shape[2]:
+        raise ValueError(f"caum_user_scores: clicked_news_vector {tuple(x.shape)} / cand_news_vector {tuple(c.shape)} must be [B, S, D] / [B, D]")
+    if c.stride(1) != 1 or (c.shape[0] > 1 and c.stride(0) < c.shape[1]):
+        c = c.contiguous()
+    if len(params) != len(CAUM_PARAMS):
+        raise ValueError(f"caum_user_scores: {len(CAUM_PARAMS)} parameters expected ({', '.join(CAUM_PARAMS)})")
+    params = [_dev(t, torch.float32, n).contiguous() for t, n in zip(params, CAUM_PARAMS)]
+    b, s, d = x.shape
+    f, u, h1, h2 = params[0].shape[0], params[2].shape[0], params[10].shape[0], params[12].shape[0]
+    if d != u:
+        raise RuntimeError(f"CAUMUserEncoder: news_vector_dim {d} != user_vector_dim {u} — DenseAttention(input_dim=2 * {u}) is fed "
+                           f"cat[all ({u}), candidate ({d})], which only the reference's D == U configuration can multiply")
+    shapes = ((f, 4 * d), (f,), (u, 2 * d), (u,), (3 * u, u), (3 * u,), (u, u), (u,), (u, f + u), (u,), (h1, 2 * u), (h1,), (h2, h1), (h2,),
+              (1, h2), (1,))
+    for t, n, want in zip(params, CAUM_PARAMS, shapes):
+        if tuple(t.shape) != want:
+            raise ValueError(f"caum_user_scores: {n} is {tuple(t.shape)}, expected {want}")
+    return x, c, params, (b, s, d, f, u, h1, h2, int(heads))
+
+
+def _caum_forward(x: Tensor, c: Tensor, params: Sequence[Tensor], dims, p: float, seed: int, site0: int):
+    b, s = dims[0], dims[1]
+    lib = _lib.load()
+    out = torch.empty(b, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        need = int(lib.manner_hip_caum_user_saved_bytes(*dims))
+        saved = _workspace(need, x.device)
+        tab = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        _lib.check(lib.manner_hip_caum_user_forward(_ptr(x), _ptr(c), c.stride(0) if b > 1 else dims[2], tab, *dims, C.c_float(p),
+                                                    C.c_uint64(seed), C.c_uint32(site0), _ptr(out), _ptr(saved), need, _stream()))
+    return out, saved, need
+
+
+def caum_user_scores(x: Tensor, c: Tensor, params: Sequence[Tensor], heads: int) -> Tensor:
+    """CAUMUserEncoder.forward in eval() (reference user_encoder.py:121-178): x [B, S, D] clicked news, c [B, D] one candidate per user
+    (any row stride), ``params`` the 16 tensors named by ``CAUM_PARAMS`` -> scores [B].  The attention runs across the B users at each
+    history slot and the softmax over all S slots, unmasked, as in the reference.  S <= 256, widths <= 1024, head dim <= 64, D == U."""
+    x, c, params, dims = _caum_operands(x, c, params, heads)
+    return _caum_forward(x, c, params, dims, 0.0, 0, CAUM_DROPOUT_SITE)[0]
+
+
+def linear_tanh(x: Tensor, weight: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """tanh(nn.Linear(x)) in one kernel on f32 rows (DenseAttention, reference attention.py:135-138): x [R, K] -> [R, O]."""
+    x = _dev(x, torch.float32, "input").contiguous()
+    weight = _dev(weight, torch.float32, "weight").contiguous()
+    r, k = x.shape
+    o = weight.shape[0]
+    assert weight.shape[1] == k
+    if bias is not None:
+        bias = _dev(bias, torch.float32, "bias").contiguous()
+    y = torch.empty((r, o), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().manner_hip_linear_tanh(_ptr(x), _ptr(weight), _ptr(bias), r, k, o, _ptr(y), _stream()))
+    return y
+
+
+def relu(x: Tensor) -> Tensor:
+    x = _dev(x, torch.float32, "x").contiguous()
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().manner_hip_relu(_ptr(x), _ptr(out), x.numel(), _stream()))
+    return out
+
+
 class HalfTable:
     """IEEE-half copy of a news-embedding table for the scorer: ``rows`` float16 [n, D] and, when centred, ``mean`` float32 [D]
     (rows = half(T - mean)); see ``table_to_f16``."""

@@ -1,5 +1,6 @@
-"""AdditiveAttention, PolyAttention, TargetAwareAttention — mirrors of reference manner/models/components/attention.py:6-29, 32-84,
-87-116 (the latter two are MINER's; ``install(baselines=("miner",))`` binds them)."""
+"""AdditiveAttention, PolyAttention, TargetAwareAttention, DenseAttention — mirrors of reference
+manner/models/components/attention.py:6-29, 32-84, 87-116, 119-141 (PolyAttention and TargetAwareAttention are MINER's,
+``install(baselines=("miner",))`` binds them; DenseAttention is CAUM's, ``install(baselines=("caum_plm",))``)."""
 from typing import Optional
 
 import torch
@@ -42,6 +43,32 @@ class PolyAttention(nn.Module):
             return train.poly_attention(clicked_news_vector, attn_mask, self.linear.weight, self.context_codes, bias)
         return hip.poly_attention(clicked_news_vector, attn_mask, self.linear.weight.detach(), self.context_codes.detach(),
                                   None if bias is None else bias.detach())
+
+
+class DenseAttention(nn.Module):
+    """reference attention.py:119-141 (CAUM's; ``install(baselines=("caum_plm",))`` binds it): Linear, tanh, Linear, tanh, Linear to one
+    logit.  ``CAUMUserEncoder`` does not call this forward — its kernels read the parameters and split the first Linear between the
+    history rows and the candidate — so this is the stand-alone operator, f32 whatever the autocast state."""
+
+    def __init__(self, input_dim: int, hidden_dim1: int, hidden_dim2: int) -> None:
+        super().__init__()
+        self.linear = nn.Linear(input_dim, hidden_dim1)
+        self.tanh1 = nn.Tanh()
+        self.linear2 = nn.Linear(hidden_dim1, hidden_dim2)
+        self.tanh2 = nn.Tanh()
+        self.linear3 = nn.Linear(hidden_dim2, 1)
+
+    def forward(self, input_vector: torch.Tensor) -> torch.Tensor:
+        """(..., input_dim) -> (..., 1)"""
+        l1, l2, l3 = self.linear, self.linear2, self.linear3
+        if _differentiable(self, input_vector):
+            t = train.linear_tanh(input_vector, l1.weight, l1.bias)
+            t = train.linear_tanh(t, l2.weight, l2.bias)
+            return train.linear(t, l3.weight, l3.bias)
+        shape = input_vector.shape
+        t = hip.linear_tanh(input_vector.reshape(-1, shape[-1]), l1.weight.detach(), l1.bias.detach())
+        t = hip.linear_tanh(t, l2.weight.detach(), l2.bias.detach())
+        return hip.linear(t, l3.weight.detach(), l3.bias.detach()).reshape(*shape[:-1], 1)
 
 
 class TargetAwareAttention(nn.Module):

@@ -655,6 +655,83 @@ class MannerNewsEncoder(nn.Module):
         return hip.linear(both, self.linear.weight.detach(), self.linear.bias.detach())
 
 
+class CAUMCategoryEncoder(nn.Module):
+    """reference news_encoder.py:331-355 (``install(baselines=("caum_plm",))`` binds it): embedding -> dropout -> Linear -> ReLU, every
+    operator on the HIP kernels with its backward; f32 whatever the autocast state."""
+
+    def __init__(self, num_categories: int, category_embedding_dim: int, category_output_dim: int, dropout_probability: float) -> None:
+        super().__init__()
+        self.category_embedding = nn.Embedding(num_embeddings=num_categories, embedding_dim=category_embedding_dim, padding_idx=0)
+        self.linear = nn.Linear(category_embedding_dim, category_output_dim)
+        self.dropout = nn.Dropout(dropout_probability)
+
+    def forward(self, category: torch.Tensor) -> torch.Tensor:
+        emb = self.category_embedding
+        p = self.dropout.p if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0
+        x = train.embedding(category, emb.weight, emb.padding_idx)
+        x = train.dropout(x, p, seed, site=10)
+        return train.relu(train.linear(x, self.linear.weight, self.linear.bias))
+
+
+class _CAUMEntityEncoder(MannerEntityEncoder):
+    """MannerEntityEncoder's operator chain with the any-head-dim attention: CAUM ships entity dim 100 with 20 heads, head dim 5, which
+    the seven-case dispatch of ``mha_axis0`` refuses.  Same parameters and state-dict keys; under no_grad the same operators record
+    nothing."""
+
+    def forward(self, entity_sequence: torch.Tensor) -> torch.Tensor:
+        mha, pool = self.multihead_attention, self.additive_attention
+        if mha.dropout != 0.0:
+            raise RuntimeError("attention-probability dropout inside nn.MultiheadAttention is not built (the reference uses 0)")
+        p = self.dropout.p if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0
+        emb = self.pretrained_embedding
+        x = train.embedding(entity_sequence, emb.weight, emb.padding_idx)
+        x = train.dropout(x, p, seed, site=2)
+        x = train.mha_axis0_any(x, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias, mha.num_heads)
+        x = train.dropout(x, p, seed, site=3)
+        return train.additive_pool(x, pool.linear.weight, pool.linear.bias, pool.query)
+
+
+class CAUMNewsEncoder(nn.Module):
+    """reference news_encoder.py:358-434 (``install(baselines=("caum_plm",))`` binds it): the PLMTextEncoder mirror, the category
+    encoder, with ``use_entities`` an entity encoder (keys ``entity_encoder.*``, any head dim), and the final Linear over their
+    concatenation."""
+
+    def __init__(self, plm_model: str, frozen_layers: List[int], text_embedding_dim: int, text_num_attention_heads: int, query_vector_dim: int,
+                 dropout_probability: float, num_categories: int, category_embedding_dim: int, use_entities: bool, entity_embeddings: nn.Embedding,
+                 entity_embedding_dim: int, entity_num_attention_heads: int, news_out_embedding_dim: int) -> None:
+        super().__init__()
+        self.text_encoder = PLMTextEncoder(plm_model=plm_model, frozen_layers=frozen_layers, text_embedding_dim=text_embedding_dim,
+                                           num_attention_heads=text_num_attention_heads, query_vector_dim=query_vector_dim,
+                                           dropout_probability=dropout_probability)
+        self.category_encoder = CAUMCategoryEncoder(num_categories=num_categories, category_embedding_dim=category_embedding_dim,
+                                                    category_output_dim=category_embedding_dim, dropout_probability=dropout_probability)
+        self.use_entities = use_entities
+        if self.use_entities:
+            pretrained_entity_embedding = nn.Embedding.from_pretrained(embeddings=torch.FloatTensor(entity_embeddings), freeze=False,
+                                                                       padding_idx=0)
+            self.entity_encoder = _CAUMEntityEncoder(pretrained_embedding=pretrained_entity_embedding, embedding_dim=entity_embedding_dim,
+                                                     num_attention_heads=entity_num_attention_heads, query_vector_dim=query_vector_dim,
+                                                     dropout_probability=dropout_probability)
+            linear_in_features = text_embedding_dim + entity_embedding_dim + category_embedding_dim
+        else:
+            linear_in_features = text_embedding_dim + category_embedding_dim
+        self.linear = nn.Linear(in_features=linear_in_features, out_features=news_out_embedding_dim)
+
+    def forward(self, news: Dict[str, Any]) -> torch.Tensor:
+        text_vector = self.text_encoder(news["text"])
+        category_vector = self.category_encoder(news["category"])
+        if self.use_entities:
+            parts = [text_vector, self.entity_encoder(news["entities"]), category_vector]
+        else:
+            parts = [text_vector, category_vector]
+        all_vectors = torch.cat(parts, dim=-1)                                  # a copy; its backward is a split
+        if _wants_graph(self.linear, all_vectors):
+            return train.linear(all_vectors, self.linear.weight, self.linear.bias)
+        return hip.linear(all_vectors, self.linear.weight.detach(), self.linear.bias.detach())
+
+
 class PLMTextEncoder(nn.Module):
     """reference news_encoder.py:132-171 — the text encoder of the PLM baselines (NRMS-PLM, TANR-PLM, SentiRec-PLM, ...).
 

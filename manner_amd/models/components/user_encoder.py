@@ -1,10 +1,11 @@
-"""NAMLUserEncoder / NRMSUserEncoder — mirror of reference manner/models/components/user_encoder.py:9-42
-(NAML: imported by the reference as ``UserEncoder``, cr_module.py:16; NRMS: the user encoder of the PLM baselines)."""
+"""NAMLUserEncoder / NRMSUserEncoder / CAUMUserEncoder — mirror of reference manner/models/components/user_encoder.py:9-42, 92-178
+(NAML: imported by the reference as ``UserEncoder``, cr_module.py:16; NRMS: the user encoder of the PLM baselines; CAUM: opt-in,
+``install(baselines=("caum_plm",))``)."""
 import torch
 import torch.nn as nn
 
 from manner_amd import hip, train
-from manner_amd.models.components.attention import AdditiveAttention
+from manner_amd.models.components.attention import AdditiveAttention, DenseAttention, _differentiable
 
 
 class NAMLUserEncoder(nn.Module):
@@ -41,3 +42,49 @@ class NRMSUserEncoder(nn.Module):
         user_vector = hip.mha_axis0(clicked_news_vector, mha.in_proj_weight.detach(), mha.in_proj_bias.detach(),
                                     mha.out_proj.weight.detach(), mha.out_proj.bias.detach(), mha.num_heads)
         return self.additive_attention(user_vector)
+
+
+class CAUMUserEncoder(nn.Module):
+    """reference user_encoder.py:92-178 — CAUM's candidate-aware user encoder (``install(baselines=("caum_plm",))`` binds it): called
+    once per candidate column with the clicked news [B, S, D] and one candidate per user [B, D] (the strided ``cand[:, i, :]`` view of
+    baselines/caum_plm_module.py, read in place), it returns the B scores.
+
+    One call is one library entry (csrc/caum.hip): the window operand [x[s-1], x[s], x[s+1], c] (circular) and [c, x[s]] are packed
+    by a kernel, never by torch; the attention runs at head dim 25 (the reference's 400 / 16) with the threads filled at small B; the
+    candidate half of the dense attention's first Linear is computed once per user.  Batch-faithful to the reference: its
+    nn.MultiheadAttention is batch_first=False but receives [B, S, U], so attention runs ACROSS THE B USERS OF THE CALL at each
+    history slot, and the softmax over the history is unmasked (zero-padded slots take part).  ``DenseAttention(input_dim=2 U)`` is fed
+    cat[all (U), candidate (D)]: as in the reference only D == U can run; construction stays legal, ``forward`` refuses D != U.
+    f32 whatever the autocast state.  The three dropouts are on in train() only and draw one seed per call from torch's CPU generator
+    (sites 7, 8, 9 of the counter-based generator)."""
+
+    def __init__(self, news_vector_dim: int, num_filters: int, dense_att_hidden_dim1: int, dense_att_hidden_dim2: int, user_vector_dim: int,
+                 num_attention_heads: int, dropout_probability: float) -> None:
+        super().__init__()
+        self.dropout1 = nn.Dropout(p=dropout_probability)
+        self.dropout2 = nn.Dropout(p=dropout_probability)
+        self.dropout3 = nn.Dropout(p=dropout_probability)
+        self.linear1 = nn.Linear(news_vector_dim * 4, num_filters)
+        self.linear2 = nn.Linear(news_vector_dim * 2, user_vector_dim)
+        self.linear3 = nn.Linear(num_filters + user_vector_dim, user_vector_dim)
+        self.dense_att = DenseAttention(input_dim=user_vector_dim * 2, hidden_dim1=dense_att_hidden_dim1, hidden_dim2=dense_att_hidden_dim2)
+        self.multihead_attention = nn.MultiheadAttention(user_vector_dim, num_attention_heads)
+
+    def _params(self):
+        mha, da = self.multihead_attention, self.dense_att
+        return [self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, mha.in_proj_weight, mha.in_proj_bias,
+                mha.out_proj.weight, mha.out_proj.bias, self.linear3.weight, self.linear3.bias, da.linear.weight, da.linear.bias,
+                da.linear2.weight, da.linear2.bias, da.linear3.weight, da.linear3.bias]
+
+    def forward(self, clicked_news_vector: torch.Tensor, cand_news_vector: torch.Tensor) -> torch.Tensor:
+        mha = self.multihead_attention
+        if mha.dropout != 0.0:
+            raise RuntimeError("attention-probability dropout inside nn.MultiheadAttention is not built (the reference uses 0)")
+        probs = {self.dropout1.p, self.dropout2.p, self.dropout3.p}
+        if len(probs) != 1:
+            raise RuntimeError("CAUMUserEncoder: the three dropouts share one probability in the reference; differing ones are not built")
+        p = self.dropout1.p if self.training else 0.0
+        if p > 0.0 or _differentiable(self, clicked_news_vector, cand_news_vector):
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0
+            return train.caum_user_scores(clicked_news_vector, cand_news_vector, self._params(), mha.num_heads, p=p, seed=seed)
+        return hip.caum_user_scores(clicked_news_vector, cand_news_vector, [t.detach() for t in self._params()], mha.num_heads)

@@ -7,6 +7,7 @@ with the HIP operator classes installed, without editing a line of the reference
 ``--baselines NAME[,NAME...]`` in front of the script path opts into further mirrored classes (``install(baselines=...)``):
 
     PYTHONPATH=<this repository> python -m manner_amd.run --baselines miner manner/train.py experiment=miner_weighted_mind
+    PYTHONPATH=<this repository> python -m manner_amd.run --baselines caum_plm manner/train.py experiment=caum_plm_mind
 
 ``install()`` runs first (manner_amd/binding.py), then the script runs as ``__main__`` with ``sys.argv`` shifted, exactly as
 ``python <script.py> [args…]`` would (the script's directory is put first on ``sys.path`` as the interpreter does; the current

@@ -631,6 +631,131 @@ def mha_axis0(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tenso
     return linear(_Axis0Attention.apply(qkv.contiguous(), int(heads)), out_proj_w, out_proj_b)
 
 
+class _Axis0AttentionAny(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv: Tensor, heads: int):
+        l0, b1, _ = qkv.shape
+        stats = torch.empty(l0 * b1 * heads * 3, dtype=torch.float32, device=qkv.device)
+        out = hip.axis0_attention_any(qkv, heads, stats)
+        ctx.save_for_backward(qkv, out, stats)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        qkv, out, stats = ctx.saved_tensors
+        l0, b1, e3 = qkv.shape
+        dqkv = torch.empty_like(qkv)
+        lib = _lib.load()
+        with torch.cuda.device(qkv.device):
+            g = _f32(g, "grad")
+            _lib.check(lib.manner_hip_axis0_attention_any_backward_q(hip._ptr(qkv), hip._ptr(out), hip._ptr(g), l0, b1, e3 // 3, ctx.heads,
+                                                                     hip._ptr(dqkv), hip._ptr(stats), hip._stream()))
+            _lib.check(lib.manner_hip_axis0_attention_any_backward_kv(hip._ptr(qkv), hip._ptr(g), hip._ptr(stats), l0, b1, e3 // 3, ctx.heads,
+                                                                      hip._ptr(dqkv), hip._stream()))
+        return dqkv, None
+
+
+def mha_axis0_any(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    """``mha_axis0`` at ANY head dim 1..64, with autograd (CAUM's entity encoder: head dim 5)."""
+    qkv = linear(x, in_proj_w, in_proj_b)
+    return linear(_Axis0AttentionAny.apply(qkv.contiguous(), int(heads)), out_proj_w, out_proj_b)
+
+
+class _CaumUser(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, c: Tensor, opts: dict, *params: Tensor):
+        out, saved, need = hip._caum_forward(x, c, [t.detach() for t in params], opts["dims"], opts["p"], opts["seed"], opts["site0"])
+        ctx.opts, ctx.saved_buf, ctx.saved_bytes = opts, saved, need
+        ctx.save_for_backward(*params)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        params = ctx.saved_tensors
+        opts = ctx.opts
+        dims = opts["dims"]
+        b, s, d = dims[:3]
+        dev = ctx.saved_buf.device
+        lib = _lib.load()
+        dx = torch.empty((b, s, d), dtype=torch.float32, device=dev)
+        dc = torch.empty((b, d), dtype=torch.float32, device=dev)
+        grads = [torch.empty_like(t) for t in params]
+        with torch.cuda.device(dev):
+            g = _f32(g, "grad")
+            need = int(lib.manner_hip_caum_user_backward_workspace_bytes(*dims))
+            ws = hip._workspace(need, dev)
+            _lib.check(lib.manner_hip_caum_user_backward(_table([t.detach() for t in params]), hip._ptr(g), *dims, C.c_float(opts["p"]),
+                                                         C.c_uint64(opts["seed"]), C.c_uint32(opts["site0"]), hip._ptr(ctx.saved_buf),
+                                                         ctx.saved_bytes, hip._ptr(dx), hip._ptr(dc), _table(grads), hip._ptr(ws), need,
+                                                         hip._stream()))
+        return (dx, dc, None, *grads)
+
+
+def caum_user_scores(x: Tensor, c: Tensor, params: Sequence[Tensor], heads: int, p: float = 0.0, seed: int = 0,
+                     site0: int = hip.CAUM_DROPOUT_SITE) -> Tensor:
+    """CAUMUserEncoder.forward (user_encoder.py:121-178) with autograd into x, c and the 16 parameters (``hip.CAUM_PARAMS`` order):
+    x [B, S, D], c [B, D] (any row stride) -> scores [B].  ``p`` > 0: dropout1 / 2 / 3 at the sites ``site0`` .. ``site0 + 2`` of the
+    counter-based generator (``dropout_mask`` returns the same bits).  The backward is hand-written from the saved activations; the K
+    third of d in_proj_bias and d dense_att.linear3.bias, zero in exact arithmetic, come back as exact zeros."""
+    x, c, params, dims = hip._caum_operands(x, c, params, heads)
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"caum_user_scores: p={p} outside [0, 1)")
+    opts = dict(dims=dims, p=float(p), seed=int(seed) & (2 ** 64 - 1), site0=int(site0))
+    return _CaumUser.apply(x, c, opts, *params)
+
+
+class _LinearTanh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, bias: Optional[Tensor]):
+        shape = x.shape
+        y = hip.linear_tanh(x.reshape(-1, shape[-1]), weight, bias)
+        ctx.save_for_backward(x, weight, y)
+        ctx.has_bias = bias is not None
+        return y.reshape(*shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, weight, y = ctx.saved_tensors
+        o, k = weight.shape
+        x2, g2 = x.reshape(-1, k), _f32(g.reshape(-1, o), "grad")
+        r = x2.shape[0]
+        lib = _lib.load()
+        dpre, dx, dw = torch.empty_like(y), torch.empty_like(x2), torch.empty_like(weight)
+        db = torch.empty(o, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+        with torch.cuda.device(x.device):
+            _lib.check(lib.manner_hip_tanh_backward(hip._ptr(y), hip._ptr(g2), hip._ptr(dpre), y.numel(), hip._stream()))
+            _lib.check(lib.manner_hip_linear_backward(hip._ptr(x2), hip._ptr(weight), hip._ptr(dpre), r, k, o, hip._ptr(None), hip._ptr(dx),
+                                                      hip._ptr(dw), hip._ptr(db), hip._stream()))
+        return dx.reshape(x.shape), dw, db
+
+
+def linear_tanh(x: Tensor, weight: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """tanh(nn.Linear(x)) with autograd (DenseAttention's first two layers, attention.py:135-138): x [..., K], weight [O, K]."""
+    return _LinearTanh.apply(_f32(x, "x"), _f32(weight, "weight"), None if bias is None else _f32(bias, "bias"))
+
+
+class _Relu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor):
+        ctx.save_for_backward(x)
+        return hip.relu(x)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (x,) = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            g = _f32(g, "grad")
+            _lib.check(_lib.load().manner_hip_relu_backward(hip._ptr(x), hip._ptr(g), hip._ptr(dx), x.numel(), hip._stream()))
+        return dx
+
+
+def relu(x: Tensor) -> Tensor:
+    """F.relu with autograd (CAUMCategoryEncoder, news_encoder.py:353)."""
+    return _Relu.apply(_f32(x, "x"))
+
+
 class _Embedding(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids: Tensor, table: Tensor, padding_idx: int):
