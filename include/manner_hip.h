@@ -697,6 +697,38 @@ int manner_hip_tanh_backward(const float* y, const float* grad_out, float* grad_
 int manner_hip_relu(const float* x, float* out, int64_t n, manner_hip_stream_t stream);
 int manner_hip_relu_backward(const float* x, const float* grad_out, float* grad_x, int64_t n, manner_hip_stream_t stream);
 
+/* ---- the LSTUR baseline's operators (csrc/gru.hip; f32, forward and backward; additive exports) ------------------------------------
+ * manner_hip_gru_forward is a one-layer nn.GRU over pack_padded_sequence(batch_first=True, enforce_sorted=False) returning
+ * `last_hidden` (manner/models/components/user_encoder.py:78-88): out[b] = the hidden state of row b after its own lengths[b] steps.
+ * x [B, S, I] is read in place at x + b x_stride_b + s x_stride_s (element strides, the features contiguous: a channel view of a wider
+ * tensor needs no copy); slots s >= lengths[b] are never read and may hold anything.  lengths int64 [B] (device); w_ih [3H, I], w_hh
+ * [3H, H], b_ih, b_hh [3H] in nn.GRU's gate order r | z | n, n = tanh(W_in x + b_in + r (W_hn h + b_hn)), h' = (1 - z) n + z h; h0
+ * [B, H] contiguous or NULL (zeros); out rows ldo floats apart (the first H columns of a wider buffer).  The input projection runs
+ * once for all rows, then one plain launch per time step (no cooperative launch, no grid barrier); a row past its length keeps h by
+ * selection.  1 <= S <= 256, 1 <= I, H <= 1024 (MANNER_HIP_E_INVALID otherwise, "gru: H=1028 unsupported (H <= 1024)").  A length
+ * outside [1, S] raises MANNER_HIP_STATUS_LENGTHS in *status (device int32, nullable): such a row takes min(max(length, 0), S) steps
+ * and nothing is read out of bounds.  workspace: manner_hip_gru_workspace_bytes (one size for forward and backward).  saved
+ * (manner_hip_gru_saved_bytes; NULL = inference): the rows of x as read, h_{t-1}, and the gates r, z, n, W_hn h + b_hn of every (t, b).
+ * manner_hip_gru_backward: from grad_out [B, H] (rows ldg apart) and `saved`, S plain launches in reverse, then grad_x [B, S, I]
+ * (contiguous; exactly 0 at the slots s >= lengths[b]), grad_h0 [B, H] (nullable), grad_w_ih, grad_w_hh, grad_b_ih, grad_b_hh.
+ * manner_hip_user_rows: out[b, :E] = m(b) src[row(b), :E] with row(b) = ids[b] (ids int64 [B] given: a gather from a table of n_rows
+ * rows ld_src apart; an id outside it raises MANNER_HIP_STATUS_INDEX and writes zeros) or row(b) = b (ids NULL: the same mask on
+ * gradient rows), m(b) = 0 or 1 / (1 - p) drawn per ROW b at (seed, site) of manner_hip_dropout_mask's generator — nn.Dropout2d on
+ * [1, B, E] as LSTURUserEncoder applies it: a whole user is masked.  out rows ld_out apart.
+ * Every reduction has a fixed order (no floating-point atomics). */
+size_t manner_hip_gru_saved_bytes(int64_t B, int64_t S, int32_t I, int32_t H);
+size_t manner_hip_gru_workspace_bytes(int64_t B, int64_t S, int32_t I, int32_t H);
+int manner_hip_gru_forward(const float* x, int64_t x_stride_b, int64_t x_stride_s, const int64_t* lengths, const float* w_ih, const float* w_hh,
+                           const float* b_ih, const float* b_hh, const float* h0, int64_t B, int64_t S, int32_t I, int32_t H, float* out,
+                           int64_t ldo, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, int32_t* status,
+                           manner_hip_stream_t stream);
+int manner_hip_gru_backward(const float* w_ih, const float* w_hh, const int64_t* lengths, const float* grad_out, int64_t ldg, int64_t B, int64_t S,
+                            int32_t I, int32_t H, void* saved, size_t saved_bytes, float* grad_x, float* grad_h0, float* grad_w_ih,
+                            float* grad_w_hh, float* grad_b_ih, float* grad_b_hh, void* workspace, size_t workspace_bytes,
+                            manner_hip_stream_t stream);
+int manner_hip_user_rows(const int64_t* ids, const float* src, int64_t n_rows, int64_t ld_src, int64_t B, int32_t E, float p, uint64_t seed,
+                         uint32_t site, float* out, int64_t ld_out, int32_t* status, manner_hip_stream_t stream);
+
 /* ---- content-addressed news-embedding cache (ABI v6, round 4; csrc/cache.hip) ----------------------------------------------
  * SURVEY.md §8(d) mode T ("each unique news encoded once per module") behind the unchanged drop-in call pattern: the reference
  * re-encodes every occurrence — manner/models/cr_module.py:107,113 call manner/models/components/news_encoder.py:29-37 per batch —

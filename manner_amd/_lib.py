@@ -142,6 +142,11 @@ SIGNATURES = {
     "manner_hip_tanh_backward": (C.c_int, [_P, _P, _P, _I64, _P]),
     "manner_hip_relu": (C.c_int, [_P, _P, _I64, _P]),
     "manner_hip_relu_backward": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "manner_hip_gru_saved_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
+    "manner_hip_gru_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
+    "manner_hip_gru_forward": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _I64, _P, _SZ, _P, _SZ, _P, _P]),
+    "manner_hip_gru_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_user_rows": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, C.c_float, C.c_uint64, C.c_uint32, _P, _I64, _P, _P]),
 }
 
 _lib = None

@@ -39,6 +39,16 @@ of the CAUM baseline (baselines/caum_plm_module.py:15-16 imports ``CAUMNewsEncod
 
 ``CAUMPLMModule``'s own lines — the per-candidate loop, ``to_dense_batch``, the loss, the metrics — stay the reference's torch.
 
+``install(baselines=("lstur_plm",))`` (configs/model/lstur_plm.yaml; the experiments lstur_{ini,con}_{mind,adressa}) rebinds the three
+leaf classes of the LSTUR baseline (baselines/lstur_plm_module.py imports ``LSTURNewsEncoder`` and ``LSTURUserEncoder``; the news
+encoder builds the category encoder):
+
+    news_encoder      LSTURCategoryEncoder, LSTURNewsEncoder
+    user_encoder      LSTURUserEncoder
+
+``LSTURPLMModule``'s own lines — ``to_dense_batch``, its Python loop for ``hist_size``, the loss, the metrics — stay the reference's
+torch.  ``MINSUserEncoder`` (a GRU after an attention of head dim 128) has no mirror.
+
 ``MINERModule`` itself is not mirrored: its category-bias construction, ``pairwise_cosine_similarity``, the max / mean aggregation
 and the disagreement loss are Lightning-level code and stay the reference's torch.  A plain ``install()`` binds exactly the first
 table, whatever an earlier call added stays until ``uninstall()``.
@@ -47,6 +57,7 @@ Use (no reference source line changes):
 
     python -m manner_amd.run manner/train.py experiment=cr_module_mind_title_scl_lf      # = install() + runpy of the script
     python -m manner_amd.run --baselines miner manner/train.py experiment=miner_weighted_mind
+    python -m manner_amd.run --baselines lstur_plm manner/train.py experiment=lstur_ini_mind
 
 or two lines at the top of ``manner/train.py`` / ``manner/eval.py``:  ``import manner_amd; manner_amd.install()``.
 """
@@ -66,6 +77,7 @@ BASELINE_TARGETS = {
     "miner": {"news_encoder": ("MINERNewsEncoder",), "attention": ("PolyAttention", "TargetAwareAttention")},
     "caum_plm": {"news_encoder": ("CAUMCategoryEncoder", "CAUMNewsEncoder"), "user_encoder": ("CAUMUserEncoder",),
                  "attention": ("DenseAttention",)},
+    "lstur_plm": {"news_encoder": ("LSTURCategoryEncoder", "LSTURNewsEncoder"), "user_encoder": ("LSTURUserEncoder",)},
 }
 _REF_PKG = "manner.models.components"
 _MIRROR_PKG = "manner_amd.models.components"
@@ -89,7 +101,8 @@ def install(reference_root: Optional[str] = None, baselines: Sequence[str] = ())
     """Rebind the mirrored classes inside the reference's ``manner.models.components`` modules.  ``reference_root``: a checkout
     of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  ``baselines``: opt-in sets of further classes
     (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention; ``"caum_plm"``: CAUMCategoryEncoder, CAUMNewsEncoder,
-    CAUMUserEncoder, DenseAttention); an unknown name raises ValueError.  Returns {module: [rebound
+    CAUMUserEncoder, DenseAttention; ``"lstur_plm"``: LSTURCategoryEncoder, LSTURNewsEncoder, LSTURUserEncoder); an unknown name raises
+    ValueError.  Returns {module: [rebound
     names]} (also the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
     targets = _targets(baselines)
     if reference_root and reference_root not in sys.path:

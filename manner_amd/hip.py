@@ -37,8 +37,9 @@ def _ptr(t: Optional[Tensor]) -> C.c_void_p:
 # ------------------------------------------------------------------ device-side input validation
 _STATUS_TEXT = {_lib.STATUS_MASK: "attention_mask is not a right-padded 0/1 prefix mask",
                 _lib.STATUS_TOKEN: "input id / position outside the embedding tables",
-                _lib.STATUS_INDEX: "news, entity or impression index outside the table (IndexError in the reference)",
-                _lib.STATUS_LENGTHS: "host_lengths disagree with attention_mask, or a batch's offsets with the data set"}
+                _lib.STATUS_INDEX: "news, entity, user or impression index outside the table (IndexError in the reference)",
+                _lib.STATUS_LENGTHS: "host_lengths disagree with attention_mask, or a batch's offsets with the data set, or a history "
+                                       "length outside [1, S] (pack_padded_sequence raises in the reference)"}
 
 
 def _status_message(flag: int) -> str:
@@ -901,6 +902,116 @@ def relu(x: Tensor) -> Tensor:
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().manner_hip_relu(_ptr(x), _ptr(out), x.numel(), _stream()))
     return out
+
+
+GRU_PARAMS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+LSTUR_PARAMS = ("long_term_user_embedding.weight",) + tuple("gru." + n for n in GRU_PARAMS)
+LSTUR_DROPOUT_SITE = 11   # the user mask of LSTURUserEncoder (7 .. 10 are CAUM's)
+
+
+def _gru_operands(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, h0: Optional[Tensor]):
+    """Checked operands of the GRU entries: (x, lengths, [w_ih, w_hh, b_ih, b_hh], h0, (B, S, I, H)).  x keeps its batch and slot
+    strides when its features are contiguous (a channel view of a wider tensor is read in place); lengths stay on the device."""
+    x = _dev(x, torch.float32, "x")
+    if x.dim() != 3:
+        raise ValueError(f"gru_last_hidden: x {tuple(x.shape)} must be [B, S, I]")
+    if (x.shape[2] > 1 and x.stride(2) != 1) or min(x.stride()) < 0:
+        x = x.contiguous()
+    b, s, i = x.shape
+    if not isinstance(lengths, torch.Tensor) or not lengths.is_cuda:
+        raise RuntimeError("lengths: expected a GPU tensor — the MANNeR HIP hot path has no CPU fallback")
+    if lengths.dtype not in (torch.int64, torch.int32) or tuple(lengths.shape) != (b,):
+        raise TypeError(f"lengths: expected int64 [{b}], got {lengths.dtype} {tuple(lengths.shape)}")
+    lengths = lengths.to(torch.int64).contiguous()
+    params = [_dev(t, torch.float32, "gru." + n).contiguous() for t, n in zip((w_ih, w_hh, b_ih, b_hh), GRU_PARAMS)]
+    h = params[1].shape[1]
+    for t, n, want in zip(params, GRU_PARAMS, ((3 * h, i), (3 * h, h), (3 * h,), (3 * h,))):
+        if tuple(t.shape) != want:
+            raise ValueError(f"gru_last_hidden: gru.{n} is {tuple(t.shape)}, expected {want}")
+    if h0 is not None:
+        h0 = _dev(h0, torch.float32, "h0").contiguous()
+        if tuple(h0.shape) != (b, h):
+            raise ValueError(f"gru_last_hidden: h0 is {tuple(h0.shape)}, expected {(b, h)}")
+    return x, lengths, params, h0, (b, s, i, h)
+
+
+def _gru_forward(x: Tensor, lengths: Tensor, params: Sequence[Tensor], h0: Optional[Tensor], dims, out: Tensor, save: bool):
+    """One manner_hip_gru_forward call into the first H columns of ``out`` [B, >= H]; -> (saved buffer or None, its size)."""
+    b, s = dims[0], dims[1]
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.manner_hip_gru_workspace_bytes(*dims))
+        ws = _workspace(need, x.device)
+        keep = int(lib.manner_hip_gru_saved_bytes(*dims)) if save else 0
+        saved = _workspace(keep, x.device) if save else None
+        _lib.check(lib.manner_hip_gru_forward(_ptr(x), x.stride(0) if b > 1 else 0, x.stride(1) if s > 1 else 0, _ptr(lengths), *[_ptr(t) for t in params],
+                                              _ptr(h0), *dims, _ptr(out), out.stride(0) if b > 1 else out.shape[1], _ptr(saved), keep, _ptr(ws), need,
+                                              _ptr(device_status(x.device).word), _stream()))
+    return saved, keep
+
+
+def gru_last_hidden(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, h0: Optional[Tensor] = None) -> Tensor:
+    """``nn.GRU`` on ``pack_padded_sequence(x, lengths, batch_first=True, enforce_sorted=False)``, ``last_hidden`` (reference
+    user_encoder.py:78-88): x [B, S, I] (batch and slot strides are read in place), lengths int64 [B] on the device, the four
+    ``nn.GRU`` tensors (gates r | z | n), h0 [B, H] or None -> [B, H], row b after its own ``lengths[b]`` steps.  Slots past a row's
+    length are never read.  One launch per time step; nothing is read back to the host.  S <= 256, I, H <= 1024; a length outside
+    [1, S] surfaces at ``check_status``."""
+    x, lengths, params, h0, dims = _gru_operands(x, lengths, w_ih, w_hh, b_ih, b_hh, h0)
+    out = torch.empty((dims[0], dims[3]), dtype=torch.float32, device=x.device)
+    _gru_forward(x, lengths, params, h0, dims, out, save=False)
+    return out
+
+
+def user_rows(ids: Optional[Tensor], src: Tensor, out: Tensor, p: float, seed: int, site: int = LSTUR_DROPOUT_SITE) -> Tensor:
+    """out[b, :E] = m(b) src[ids[b], :E] (``ids`` None: src[b, :E]), m(b) = 0 or 1 / (1 - p) per ROW b at (seed, site) —
+    ``nn.Dropout2d`` on [1, B, E]: a whole user is masked.  ``src`` and ``out`` are 2-D with contiguous columns (row strides kept)."""
+    b, e = out.shape
+    n_rows = src.shape[0]
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().manner_hip_user_rows(_ptr(ids), _ptr(src), n_rows, src.stride(0) if n_rows > 1 else e, b, e, C.c_float(p),
+                                                    C.c_uint64(seed), C.c_uint32(site), _ptr(out), out.stride(0) if b > 1 else e,
+                                                    _ptr(device_status(out.device).word), _stream()))
+    return out
+
+
+def _lstur_operands(user: Tensor, x: Tensor, lengths: Tensor, params: Sequence[Tensor], method: str):
+    if method not in ("ini", "con"):
+        raise ValueError(f"lstur_user: long_short_term_method {method!r} (ini or con)")
+    if len(params) != len(LSTUR_PARAMS):
+        raise ValueError(f"lstur_user: {len(LSTUR_PARAMS)} parameters expected ({', '.join(LSTUR_PARAMS)})")
+    table = _dev(params[0], torch.float32, LSTUR_PARAMS[0]).contiguous()
+    x, lengths, gru, _, dims = _gru_operands(x, lengths, *params[1:], None)
+    user = _dev(user, torch.int64, "user").contiguous()
+    if tuple(user.shape) != (dims[0],) or table.dim() != 2 or table.shape[1] != dims[3]:
+        raise ValueError(f"lstur_user: user {tuple(user.shape)} / {LSTUR_PARAMS[0]} {tuple(table.shape)} must be [{dims[0]}] / [num_users, {dims[3]}]")
+    return user, x, lengths, table, gru, dims
+
+
+def _lstur_forward(user, x, lengths, table, gru, dims, method: str, p: float, seed: int, save: bool):
+    """-> (out, saved, saved bytes).  ``ini``: the masked user rows are h0; ``con``: they are the second half of the output buffer and
+    the GRU writes its first half, so no concatenation runs."""
+    b, h = dims[0], dims[3]
+    if method == "ini":
+        out = torch.empty((b, h), dtype=torch.float32, device=x.device)
+        h0 = user_rows(user, table, torch.empty((b, h), dtype=torch.float32, device=x.device), p, seed)
+    else:
+        out = torch.empty((b, 2 * h), dtype=torch.float32, device=x.device)
+        h0 = None
+        if b:
+            user_rows(user, table, out[:, h:], p, seed)
+    saved, keep = _gru_forward(x, lengths, gru, h0, dims, out, save)
+    return out, saved, keep
+
+
+def lstur_user(user: Tensor, x: Tensor, lengths: Tensor, params: Sequence[Tensor], method: str, p: float = 0.0, seed: int = 0) -> Tensor:
+    """LSTURUserEncoder.forward (reference user_encoder.py:70-89): user int64 [B], x [B, S, I] clicked news, lengths int64 [B],
+    ``params`` the five tensors named by ``LSTUR_PARAMS``.  ``ini``: the GRU starts from the user's embedding row -> [B, H];
+    ``con``: it starts from zero and the row is appended -> [B, 2 H].  ``p`` > 0 masks whole users (``nn.Dropout2d`` on [1, B, E]) at
+    (seed, row).  A user id outside the table or a length outside [1, S] surfaces at ``check_status``."""
+    user, x, lengths, table, gru, dims = _lstur_operands(user, x, lengths, params, method)
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"lstur_user: p={p} outside [0, 1)")
+    return _lstur_forward(user, x, lengths, table, gru, dims, method, float(p), int(seed) & (2 ** 64 - 1), save=False)[0]
 
 
 class HalfTable:

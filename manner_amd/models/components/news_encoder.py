@@ -1,5 +1,5 @@
-"""MannerTextEncoder / MannerEntityEncoder / MannerNewsEncoder / PLMTextEncoder / MINERNewsEncoder — mirror of reference
-manner/models/components/news_encoder.py:11-171, 297-328.
+"""MannerTextEncoder / MannerEntityEncoder / MannerNewsEncoder / PLMTextEncoder / MINERNewsEncoder, and the opt-in LSTUR and CAUM
+news encoders — mirror of reference manner/models/components/news_encoder.py:11-171, 239-434.
 
 Same constructor arguments, forward signature and state_dict keys (``text_encoder.plm_model.*`` are
 the HF BertModel / RobertaModel names), so reference checkpoints load with
@@ -730,6 +730,37 @@ class CAUMNewsEncoder(nn.Module):
         if _wants_graph(self.linear, all_vectors):
             return train.linear(all_vectors, self.linear.weight, self.linear.bias)
         return hip.linear(all_vectors, self.linear.weight.detach(), self.linear.bias.detach())
+
+
+class LSTURCategoryEncoder(nn.Module):
+    """reference news_encoder.py:239-255 (``install(baselines=("lstur_plm",))`` binds it): an embedding lookup with ``padding_idx=0`` on the
+    HIP embedding entry, forward and backward (row 0 receives no gradient; an id outside the table raises at the next status check)."""
+
+    def __init__(self, num_categories: int, category_embedding_dim: int) -> None:
+        super().__init__()
+        self.category_embedding = nn.Embedding(num_embeddings=num_categories, embedding_dim=category_embedding_dim, padding_idx=0)
+
+    def forward(self, category: torch.Tensor) -> torch.Tensor:
+        emb = self.category_embedding
+        return train.embedding(category, emb.weight, emb.padding_idx)
+
+
+class LSTURNewsEncoder(nn.Module):
+    """reference news_encoder.py:258-294 (``install(baselines=("lstur_plm",))`` binds it): cat(PLMTextEncoder(text), category embedding)
+    along dim 1 — the PLMTextEncoder mirror below and the category rows, copied into the two column ranges of one [N, T + C] buffer."""
+
+    def __init__(self, plm_model: str, frozen_layers: List[int], text_embedding_dim: int, num_attention_heads: int, query_vector_dim: int,
+                 dropout_probability: float, num_categories: int, category_embedding_dim: int) -> None:
+        super().__init__()
+        self.text_encoder = PLMTextEncoder(plm_model=plm_model, frozen_layers=frozen_layers, text_embedding_dim=text_embedding_dim,
+                                           num_attention_heads=num_attention_heads, query_vector_dim=query_vector_dim,
+                                           dropout_probability=dropout_probability)
+        self.category_encoder = LSTURCategoryEncoder(num_categories=num_categories, category_embedding_dim=category_embedding_dim)
+
+    def forward(self, news: Dict[str, Any]) -> torch.Tensor:
+        text_vector = self.text_encoder(news["text"])
+        category_vector = self.category_encoder(news["category"])
+        return torch.cat([text_vector, category_vector], dim=1)                 # a copy; its backward is a split
 
 
 class PLMTextEncoder(nn.Module):

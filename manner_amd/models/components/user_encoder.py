@@ -1,6 +1,6 @@
-"""NAMLUserEncoder / NRMSUserEncoder / CAUMUserEncoder — mirror of reference manner/models/components/user_encoder.py:9-42, 92-178
-(NAML: imported by the reference as ``UserEncoder``, cr_module.py:16; NRMS: the user encoder of the PLM baselines; CAUM: opt-in,
-``install(baselines=("caum_plm",))``)."""
+"""NAMLUserEncoder / NRMSUserEncoder / LSTURUserEncoder / CAUMUserEncoder — mirror of reference
+manner/models/components/user_encoder.py:9-89, 92-178 (NAML: imported by the reference as ``UserEncoder``, cr_module.py:16; NRMS: the
+user encoder of the PLM baselines; LSTUR and CAUM: opt-in, ``install(baselines=("lstur_plm",))`` / ``("caum_plm",)``)."""
 import torch
 import torch.nn as nn
 
@@ -42,6 +42,46 @@ class NRMSUserEncoder(nn.Module):
         user_vector = hip.mha_axis0(clicked_news_vector, mha.in_proj_weight.detach(), mha.in_proj_bias.detach(),
                                     mha.out_proj.weight.detach(), mha.out_proj.bias.detach(), mha.num_heads)
         return self.additive_attention(user_vector)
+
+
+class LSTURUserEncoder(nn.Module):
+    """reference user_encoder.py:45-89 — LSTUR's long- and short-term user encoder (``install(baselines=("lstur_plm",))`` binds it):
+    ``forward(user [B], clicked_news_vector [B, S, I], hist_size [B])`` returns every user's GRU state after its own ``hist_size[b]``
+    steps — what the reference gets from ``pack_padded_sequence(enforce_sorted=False)`` and ``last_hidden`` — started from the user's
+    embedding row (``ini`` -> [B, I]) or from zero with the row appended (``con`` -> [B, 2 (I // 2)]).
+
+    One call is the gather of the user rows, the input projection and one launch per history slot (csrc/gru.hip); ``hist_size`` is read
+    on the device, never copied to the host, and slots past it are never read.  The parameters live in an ``nn.Embedding`` and an
+    ``nn.GRU`` of the reference's shapes, so the state-dict keys are the reference's; neither module's own forward runs.
+    ``nn.Dropout2d`` on the [1, B, E] rows masks WHOLE USERS in train() (one draw per user and call, scaled by 1 / (1 - p)); the mirror
+    does the same from one seed per call off torch's CPU generator, without torch's warning about the 3-D input.  Row 0 of the table is
+    ``padding_idx``: it receives no gradient.  f32 whatever the autocast state.  A length outside [1, S] or a user id outside the table
+    raises at the next ``hip.check_status()`` / status poll, as the other mirrors' input errors do."""
+
+    def __init__(self, num_users: int, input_dim: int, user_masking_probability: float, long_short_term_method: str) -> None:
+        super().__init__()
+        assert long_short_term_method in ["ini", "con"]
+        self.long_short_term_method = long_short_term_method
+        hidden = input_dim if long_short_term_method == "ini" else int(input_dim * 0.5)
+        self.long_term_user_embedding = nn.Embedding(num_embeddings=num_users, embedding_dim=hidden, padding_idx=0)
+        self.dropout = nn.Dropout2d(p=user_masking_probability)
+        self.gru = nn.GRU(input_dim, hidden)
+
+    def _params(self):
+        g = self.gru
+        return [self.long_term_user_embedding.weight, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0]
+
+    def forward(self, user: torch.Tensor, clicked_news_vector: torch.Tensor, hist_size: torch.Tensor) -> torch.Tensor:
+        dev = clicked_news_vector.device
+        hip.status_poll(dev)
+        p = self.dropout.p if self.training else 0.0
+        if p > 0.0 or _differentiable(self, clicked_news_vector):
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0
+            out = train.lstur_user(user, clicked_news_vector, hist_size, self._params(), self.long_short_term_method, p=p, seed=seed)
+        else:
+            out = hip.lstur_user(user, clicked_news_vector, hist_size, [t.detach() for t in self._params()], self.long_short_term_method)
+        hip.status_arm(dev)
+        return out
 
 
 class CAUMUserEncoder(nn.Module):

@@ -705,6 +705,86 @@ def caum_user_scores(x: Tensor, c: Tensor, params: Sequence[Tensor], heads: int,
     return _CaumUser.apply(x, c, opts, *params)
 
 
+def _gru_backward(ctx, g: Tensor, want_h0: bool):
+    """manner_hip_gru_backward from the buffers ``ctx`` kept: g [B, >= H] (its first H columns are d last_hidden) ->
+    (dx, dh0 or None, [dw_ih, dw_hh, db_ih, db_hh])."""
+    lengths, w_ih, w_hh = ctx.saved_tensors[:3]
+    b, s, i, h = dims = ctx.dims
+    dev = ctx.saved_buf.device
+    lib = _lib.load()
+    dx = torch.empty((b, s, i), dtype=torch.float32, device=dev)
+    dh0 = torch.empty((b, h), dtype=torch.float32, device=dev) if want_h0 else None
+    grads = [torch.empty((3 * h, i), dtype=torch.float32, device=dev), torch.empty((3 * h, h), dtype=torch.float32, device=dev),
+             torch.empty(3 * h, dtype=torch.float32, device=dev), torch.empty(3 * h, dtype=torch.float32, device=dev)]
+    with torch.cuda.device(dev):
+        need = int(lib.manner_hip_gru_workspace_bytes(*dims))
+        ws = hip._workspace(need, dev)
+        _lib.check(lib.manner_hip_gru_backward(hip._ptr(w_ih), hip._ptr(w_hh), hip._ptr(lengths), hip._ptr(g), g.stride(0) if b > 1 else g.shape[1],
+                                               *dims, hip._ptr(ctx.saved_buf), ctx.saved_bytes, hip._ptr(dx), hip._ptr(dh0), *[hip._ptr(t) for t in grads],
+                                               hip._ptr(ws), need, hip._stream()))
+    return dx, dh0, grads
+
+
+class _GruLastHidden(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, lengths: Tensor, dims, h0: Optional[Tensor], *params: Tensor):
+        gru = [t.detach() for t in params]
+        out = torch.empty((dims[0], dims[3]), dtype=torch.float32, device=x.device)
+        ctx.saved_buf, ctx.saved_bytes = hip._gru_forward(x, lengths, gru, None if h0 is None else h0.detach(), dims, out, save=True)
+        ctx.dims, ctx.has_h0 = dims, h0 is not None
+        ctx.save_for_backward(lengths, params[0], params[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        dx, dh0, grads = _gru_backward(ctx, _f32(g, "grad"), ctx.has_h0)
+        return (dx, None, None, dh0, *grads)
+
+
+def gru_last_hidden(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, h0: Optional[Tensor] = None) -> Tensor:
+    """``hip.gru_last_hidden`` with autograd into x, the four ``nn.GRU`` tensors and h0: the forward keeps the gates of every step, the
+    backward is S plain launches in reverse and the stacked weight gradients.  d x is exactly 0 at the slots past a row's length."""
+    x, lengths, params, h0, dims = hip._gru_operands(x, lengths, w_ih, w_hh, b_ih, b_hh, h0)
+    return _GruLastHidden.apply(x, lengths, dims, h0, *params)
+
+
+class _LsturUser(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, user: Tensor, x: Tensor, lengths: Tensor, opts: dict, table: Tensor, *params: Tensor):
+        out, ctx.saved_buf, ctx.saved_bytes = hip._lstur_forward(user, x, lengths, table.detach(), [t.detach() for t in params], opts["dims"],
+                                                                 opts["method"], opts["p"], opts["seed"], save=True)
+        ctx.dims, ctx.opts, ctx.rows = opts["dims"], opts, table.shape[0]
+        ctx.save_for_backward(lengths, params[0], params[1], user)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        g = _f32(g, "grad")
+        opts, user = ctx.opts, ctx.saved_tensors[3]
+        b, h = ctx.dims[0], ctx.dims[3]
+        ini = opts["method"] == "ini"
+        dx, dh0, grads = _gru_backward(ctx, g, ini)
+        if not ctx.needs_input_grad[4]:                # a frozen table: no [num_users, E] gradient is built
+            return (None, dx, None, None, None, *grads)
+        # the user rows' gradient (ini: d h0; con: the second half of g) through the mask, then into the rows of the table
+        drows = hip.user_rows(None, dh0 if ini else g[:, h:], torch.empty((b, h), dtype=torch.float32, device=g.device), opts["p"], opts["seed"])
+        dtable = torch.empty((ctx.rows, h), dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(_lib.load().manner_hip_embedding_backward(hip._ptr(user), b, hip._ptr(drows), ctx.rows, h, 0, hip._ptr(dtable), hip._stream()))
+        return (None, dx, None, None, dtable, *grads)
+
+
+def lstur_user(user: Tensor, x: Tensor, lengths: Tensor, params: Sequence[Tensor], method: str, p: float = 0.0, seed: int = 0) -> Tensor:
+    """LSTURUserEncoder.forward (user_encoder.py:70-89) with autograd into x and the five parameters (``hip.LSTUR_PARAMS`` order).
+    ``p`` > 0: whole users are masked at (seed, row) (``nn.Dropout2d`` on [1, B, E]); the mask scale is applied to the incoming
+    gradient before ``manner_hip_embedding_backward`` (row 0, the padding row, receives nothing; a repeated user's rows add up)."""
+    user, x, lengths, table, gru, dims = hip._lstur_operands(user, x, lengths, params, method)
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"lstur_user: p={p} outside [0, 1)")
+    opts = dict(dims=dims, method=method, p=float(p), seed=int(seed) & (2 ** 64 - 1))
+    return _LsturUser.apply(user, x, lengths, opts, table, *gru)
+
+
 class _LinearTanh(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, weight: Tensor, bias: Optional[Tensor]):
