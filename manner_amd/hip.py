@@ -1220,7 +1220,9 @@ def aspect_metrics(topk: Tensor, cand_aspect: Tensor, cand_off: Tensor, num_clas
 def auc(scores: Tensor, labels: Tensor, sigmoid_rule: bool = True, return_counts: bool = False):
     """Global binary AUC over every (score, label) pair — torchmetrics ``AUROC(task="binary")`` as the
     reference feeds it (cr_module.py:81, :267-273).  Returns a float64 scalar tensor on the device (and, with
-    ``return_counts``, the exact int64 triple ``[2U, P, N]``)."""
+    ``return_counts``, the exact int64 triple ``[2U, P, N]``).  -0 and +0 are one threshold, denormals are kept apart.
+    Known divergence: NaN *scores*.  torchmetrics treats every NaN as a threshold of its own (NaN != NaN); here NaNs of equal bits
+    tie and sort past +inf (negative-sign NaNs below -inf).  Scores are expected to be NaN-free."""
     scores = _dev(scores, torch.float32, "scores").contiguous().reshape(-1)
     labels = _dev(labels, torch.float32, "labels").contiguous().reshape(-1)
     n = scores.numel()
