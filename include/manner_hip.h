@@ -729,6 +729,47 @@ int manner_hip_gru_backward(const float* w_ih, const float* w_hh, const int64_t*
 int manner_hip_user_rows(const int64_t* ids, const float* src, int64_t n_rows, int64_t ld_src, int64_t B, int32_t E, float p, uint64_t seed,
                          uint32_t site, float* out, int64_t ld_out, int32_t* status, manner_hip_stream_t stream);
 
+/* ---- the MINS baseline's operators (csrc/mins.hip; f32, forward and backward; additive exports) -------------------------------------
+ * manner_hip_channel_gru_forward is MINSUserEncoder's multi-channel GRU (manner/models/components/user_encoder.py:217-238): a one-layer
+ * GRU over R = B C independent sequences that SHARE one w_ih [3H, I], w_hh [3H, H], b_ih, b_hh [3H] (gate order r | z | n, the formulas
+ * of manner_hip_gru_forward, zero initial state).  Row r = b C + c reads x + b x_stride_b + t x_stride_s + c I (element strides: a
+ * contiguous [B, S, C I] tensor is read in place, channel c = torch.chunk's c-th piece), takes lengths[b] steps (int64 [B], device) and
+ * writes out[b, c H : (c + 1) H], rows ldo floats apart.  Slots t >= lengths[b] are never read and may hold anything; a row keeps h by
+ * selection once its length is reached.  The input projection of all (b, t, c) rows is one launch and the WHOLE RECURRENCE IS ONE
+ * LAUNCH: a workgroup of 3 x 128 threads holds W_hh in registers (thread = (gate, unit), one row of 128) and walks all S steps of its
+ * tile of 8 rows with workgroup barriers only — no cooperative launch, no grid barrier, no inter-workgroup counter.
+ * 1 <= S <= 256, 1 <= I <= 1024, 1 <= H <= 128, C >= 1, B C S within int32 (MANNER_HIP_E_INVALID otherwise, "channel_gru: H=129
+ * unsupported (H <= 128)").  A length outside [1, S] raises MANNER_HIP_STATUS_LENGTHS in *status (device int32, nullable): such a row
+ * takes min(max(length, 0), S) steps and nothing is read out of bounds.  workspace: manner_hip_channel_gru_workspace_bytes (one size
+ * for forward and backward).  saved (manner_hip_channel_gru_saved_bytes; NULL = inference), all in (b, t, c) row order: the rows of x
+ * as read, the state entering every step, and the gates r, z, n, W_hn h + b_hn of the steps taken.
+ * manner_hip_channel_gru_backward: from grad_out [B, C H] (rows ldg apart) and `saved`, ONE launch walks t = S - 1 .. 0 (thread = (gate,
+ * unit k) holds column k of W_g; the three partial products are added through LDS in the order r, z, n; dh_{t-1} = dh_t z + that sum),
+ * then manner_hip_linear_backward over the B S C stacked rows gives grad_w_hh, grad_b_hh, grad_w_ih, grad_b_ih — one fixed-order row
+ * sum over all channels — and grad_x [B, S, C I] (contiguous; exactly 0 at the slots t >= lengths[b]).
+ * manner_hip_axis0_attention_wide / _wide_backward_q / _wide_backward_kv are the manner_hip_axis0_attention_any entries at head dims
+ * 65 <= E / heads <= 128 (MINS ships 768 / 6 = 128): the same layouts, the same stats [L0 * B1 * heads * 3] protocol (_backward_q
+ * before _backward_kv) and the same arithmetic, with the lanes of a wave along the head dim (a wave per query row; backward-kv: per key
+ * row) and the other side's rows staged in LDS tiles.  Any other head dim: MANNER_HIP_E_INVALID, "axis0_attention_wide: head_dim 129
+ * unsupported (65 <= head_dim <= 128)".
+ * Every reduction has a fixed order (no floating-point atomics): the same inputs give the same bits. */
+size_t manner_hip_channel_gru_saved_bytes(int64_t B, int64_t S, int32_t C, int32_t I, int32_t H);
+size_t manner_hip_channel_gru_workspace_bytes(int64_t B, int64_t S, int32_t C, int32_t I, int32_t H);
+int manner_hip_channel_gru_forward(const float* x, int64_t x_stride_b, int64_t x_stride_s, const int64_t* lengths, const float* w_ih,
+                                   const float* w_hh, const float* b_ih, const float* b_hh, int64_t B, int64_t S, int32_t C, int32_t I, int32_t H,
+                                   float* out, int64_t ldo, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes,
+                                   int32_t* status, manner_hip_stream_t stream);
+int manner_hip_channel_gru_backward(const float* w_ih, const float* w_hh, const int64_t* lengths, const float* grad_out, int64_t ldg, int64_t B,
+                                    int64_t S, int32_t C, int32_t I, int32_t H, void* saved, size_t saved_bytes, float* grad_x, float* grad_w_ih,
+                                    float* grad_w_hh, float* grad_b_ih, float* grad_b_hh, void* workspace, size_t workspace_bytes,
+                                    manner_hip_stream_t stream);
+int manner_hip_axis0_attention_wide(const float* qkv, int64_t L0, int64_t B1, int32_t E, int32_t heads, float* out, float* stats,
+                                    manner_hip_stream_t stream);
+int manner_hip_axis0_attention_wide_backward_q(const float* qkv, const float* out, const float* grad_out, int64_t L0, int64_t B1, int32_t E,
+                                               int32_t heads, float* grad_qkv, float* stats, manner_hip_stream_t stream);
+int manner_hip_axis0_attention_wide_backward_kv(const float* qkv, const float* grad_out, const float* stats, int64_t L0, int64_t B1, int32_t E,
+                                                int32_t heads, float* grad_qkv, manner_hip_stream_t stream);
+
 /* ---- content-addressed news-embedding cache (ABI v6, round 4; csrc/cache.hip) ----------------------------------------------
  * SURVEY.md §8(d) mode T ("each unique news encoded once per module") behind the unchanged drop-in call pattern: the reference
  * re-encodes every occurrence — manner/models/cr_module.py:107,113 call manner/models/components/news_encoder.py:29-37 per batch —

@@ -147,6 +147,13 @@ SIGNATURES = {
     "manner_hip_gru_forward": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _I64, _P, _SZ, _P, _SZ, _P, _P]),
     "manner_hip_gru_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "manner_hip_user_rows": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, C.c_float, C.c_uint64, C.c_uint32, _P, _I64, _P, _P]),
+    "manner_hip_channel_gru_saved_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),
+    "manner_hip_channel_gru_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),
+    "manner_hip_channel_gru_forward": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P, _I64, _P, _SZ, _P, _SZ, _P, _P]),
+    "manner_hip_channel_gru_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_axis0_attention_wide": (C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    "manner_hip_axis0_attention_wide_backward_q": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    "manner_hip_axis0_attention_wide_backward_kv": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P]),
 }
 
 _lib = None

@@ -13,7 +13,7 @@ them, exactly the classes this build mirrors:
 
 Everything else of those files — ``NAMLNewsEncoder``, ``LSTURNewsEncoder``, ``MINERNewsEncoder``, ``CAUMNewsEncoder``,
 ``PolyAttention``, ``TargetAwareAttention``, ``DenseAttention``, ``LSTURUserEncoder``, ``CAUMUserEncoder``, ``MINSUserEncoder`` —
-stays the reference's own torch code by default, and so do the names those classes captured at import time (the reference's
+stays the reference's own torch code by default (each has an opt-in below), and so do the names those classes captured at import time (the reference's
 ``NAMLNewsEncoder`` keeps using the reference's ``AdditiveAttention``: its module-level binding inside ``news_encoder`` is an import
 of the ORIGINAL class object and is only replaced where it is one of the listed names of that module).  ``manner.utils``,
 ``manner.data``, ``manner.models.cr_module`` … are never touched: there is no ``manner`` package in this repository that could
@@ -47,7 +47,17 @@ encoder builds the category encoder):
     user_encoder      LSTURUserEncoder
 
 ``LSTURPLMModule``'s own lines — ``to_dense_batch``, its Python loop for ``hist_size``, the loss, the metrics — stay the reference's
-torch.  ``MINSUserEncoder`` (a GRU after an attention of head dim 128) has no mirror.
+torch.
+
+``install(baselines=("mins_plm",))`` (configs/model/mins_plm.yaml; the experiment mins_mind) rebinds the three leaf classes of the MINS
+baseline (baselines/mins_plm_module.py imports ``NAMLNewsEncoder`` and ``MINSUserEncoder`` as ``NewsEncoder`` / ``UserEncoder``; the
+news encoder builds the category encoder):
+
+    news_encoder      NAMLCategoryEncoder, NAMLNewsEncoder
+    user_encoder      MINSUserEncoder
+
+``install(baselines=("naml_plm",))`` (configs/model/naml_plm.yaml; naml_mind) rebinds the two news-side classes alone — NAML-PLM's user
+encoder, ``NAMLUserEncoder``, is bound by every install.  ``MINSPLMModule`` / ``NAMLPLMModule``'s own lines stay the reference's torch.
 
 ``MINERModule`` itself is not mirrored: its category-bias construction, ``pairwise_cosine_similarity``, the max / mean aggregation
 and the disagreement loss are Lightning-level code and stay the reference's torch.  A plain ``install()`` binds exactly the first
@@ -58,6 +68,7 @@ Use (no reference source line changes):
     python -m manner_amd.run manner/train.py experiment=cr_module_mind_title_scl_lf      # = install() + runpy of the script
     python -m manner_amd.run --baselines miner manner/train.py experiment=miner_weighted_mind
     python -m manner_amd.run --baselines lstur_plm manner/train.py experiment=lstur_ini_mind
+    python -m manner_amd.run --baselines mins_plm manner/train.py experiment=mins_mind
 
 or two lines at the top of ``manner/train.py`` / ``manner/eval.py``:  ``import manner_amd; manner_amd.install()``.
 """
@@ -78,6 +89,8 @@ BASELINE_TARGETS = {
     "caum_plm": {"news_encoder": ("CAUMCategoryEncoder", "CAUMNewsEncoder"), "user_encoder": ("CAUMUserEncoder",),
                  "attention": ("DenseAttention",)},
     "lstur_plm": {"news_encoder": ("LSTURCategoryEncoder", "LSTURNewsEncoder"), "user_encoder": ("LSTURUserEncoder",)},
+    "mins_plm": {"news_encoder": ("NAMLCategoryEncoder", "NAMLNewsEncoder"), "user_encoder": ("MINSUserEncoder",)},
+    "naml_plm": {"news_encoder": ("NAMLCategoryEncoder", "NAMLNewsEncoder")},
 }
 _REF_PKG = "manner.models.components"
 _MIRROR_PKG = "manner_amd.models.components"
@@ -101,7 +114,8 @@ def install(reference_root: Optional[str] = None, baselines: Sequence[str] = ())
     """Rebind the mirrored classes inside the reference's ``manner.models.components`` modules.  ``reference_root``: a checkout
     of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  ``baselines``: opt-in sets of further classes
     (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention; ``"caum_plm"``: CAUMCategoryEncoder, CAUMNewsEncoder,
-    CAUMUserEncoder, DenseAttention; ``"lstur_plm"``: LSTURCategoryEncoder, LSTURNewsEncoder, LSTURUserEncoder); an unknown name raises
+    CAUMUserEncoder, DenseAttention; ``"lstur_plm"``: LSTURCategoryEncoder, LSTURNewsEncoder, LSTURUserEncoder; ``"mins_plm"``:
+    NAMLCategoryEncoder, NAMLNewsEncoder, MINSUserEncoder; ``"naml_plm"``: NAMLCategoryEncoder, NAMLNewsEncoder); an unknown name raises
     ValueError.  Returns {module: [rebound
     names]} (also the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
     targets = _targets(baselines)

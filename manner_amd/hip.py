@@ -1014,6 +1014,114 @@ def lstur_user(user: Tensor, x: Tensor, lengths: Tensor, params: Sequence[Tensor
     return _lstur_forward(user, x, lengths, table, gru, dims, method, float(p), int(seed) & (2 ** 64 - 1), save=False)[0]
 
 
+MINS_PARAMS = ("multihead_attention.in_proj_weight", "multihead_attention.in_proj_bias", "multihead_attention.out_proj.weight",
+               "multihead_attention.out_proj.bias") + tuple("gru." + n for n in GRU_PARAMS)
+AXIS0_WIDE_MIN_DH = 65      # head dims 65 .. 128 are axis0_attention_wide's; 1 .. 64 are axis0_attention_any's
+
+
+def _channel_gru_operands(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, channels: int):
+    """Checked operands of the channel-GRU entries: (x, lengths, [w_ih, w_hh, b_ih, b_hh], (B, S, C, I, H)).  x [B, S, C I] keeps its
+    batch and slot strides when its features are contiguous; lengths stay on the device."""
+    x = _dev(x, torch.float32, "x")
+    c = int(channels)
+    if x.dim() != 3 or c < 1 or x.shape[2] % c:
+        raise ValueError(f"channel_gru_last_hidden: x {tuple(x.shape)} must be [B, S, C I] with C = {channels} channels")
+    if (x.shape[2] > 1 and x.stride(2) != 1) or min(x.stride()) < 0:
+        x = x.contiguous()
+    b, s, width = x.shape
+    i = width // c
+    if not isinstance(lengths, torch.Tensor) or not lengths.is_cuda:
+        raise RuntimeError("lengths: expected a GPU tensor — the MANNeR HIP hot path has no CPU fallback")
+    if lengths.dtype not in (torch.int64, torch.int32) or tuple(lengths.shape) != (b,):
+        raise TypeError(f"lengths: expected int64 [{b}], got {lengths.dtype} {tuple(lengths.shape)}")
+    lengths = lengths.to(torch.int64).contiguous()
+    params = [_dev(t, torch.float32, "gru." + n).contiguous() for t, n in zip((w_ih, w_hh, b_ih, b_hh), GRU_PARAMS)]
+    h = params[1].shape[1]
+    for t, n, want in zip(params, GRU_PARAMS, ((3 * h, i), (3 * h, h), (3 * h,), (3 * h,))):
+        if tuple(t.shape) != want:
+            raise ValueError(f"channel_gru_last_hidden: gru.{n} is {tuple(t.shape)}, expected {want}")
+    return x, lengths, params, (b, s, c, i, h)
+
+
+def _channel_gru_forward(x: Tensor, lengths: Tensor, params: Sequence[Tensor], dims, save: bool):
+    """One manner_hip_channel_gru_forward call -> (out [B, C H], saved buffer or None, its size)."""
+    b, s, c, _, h = dims
+    lib = _lib.load()
+    out = torch.empty((b, c * h), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        need = int(lib.manner_hip_channel_gru_workspace_bytes(*dims))
+        ws = _workspace(need, x.device)
+        keep = int(lib.manner_hip_channel_gru_saved_bytes(*dims)) if save else 0
+        saved = _workspace(keep, x.device) if save else None
+        _lib.check(lib.manner_hip_channel_gru_forward(_ptr(x), x.stride(0) if b > 1 else 0, x.stride(1) if s > 1 else 0, _ptr(lengths),
+                                                      *[_ptr(t) for t in params], *dims, _ptr(out), c * h, _ptr(saved), keep, _ptr(ws), need,
+                                                      _ptr(device_status(x.device).word), _stream()))
+    return out, saved, keep
+
+
+def channel_gru_last_hidden(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, channels: int) -> Tensor:
+    """MINSUserEncoder's multi-channel GRU (reference user_encoder.py:217-238): x [B, S, C I] is C channels of width I (``torch.chunk``
+    along the features, read in place), every channel through the SAME ``nn.GRU`` tensors (gates r | z | n) on
+    ``pack_padded_sequence(lengths, enforce_sorted=False)``, ``last_hidden`` concatenated -> [B, C H].  lengths int64 [B] on the device;
+    slots past a row's length are never read.  The whole recurrence is one launch (csrc/mins.hip); nothing is read back to the host.
+    S <= 256, I <= 1024, H <= 128; a length outside [1, S] surfaces at ``check_status``."""
+    x, lengths, params, dims = _channel_gru_operands(x, lengths, w_ih, w_hh, b_ih, b_hh, channels)
+    return _channel_gru_forward(x, lengths, params, dims, save=False)[0]
+
+
+def axis0_attention_wide(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
+    """``axis0_attention_any`` at head dims 65 .. 128 (MINS ships 768 / 6 = 128): qkv [L0, B1, 3E] -> [L0, B1, E]; a wave per query
+    row, the lanes along the head dim.  ``stats`` f32 [L0 * B1 * heads * 3] receives the softmax statistics the backward reads."""
+    qkv = _dev(qkv, torch.float32, "qkv").contiguous()
+    l0, b1, e3 = qkv.shape
+    out = torch.empty((l0, b1, e3 // 3), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.load().manner_hip_axis0_attention_wide(_ptr(qkv), l0, b1, e3 // 3, int(heads), _ptr(out), _ptr(stats), _stream()))
+    return out
+
+
+def mha_axis0_wide(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    """``mha_axis0_any`` at head dims 65 .. 128: attention along AXIS 0 of x [L0, B1, E], unmasked."""
+    x = _dev(x, torch.float32, "x").contiguous()
+    l0, b1, e = x.shape
+    if x.numel() == 0:
+        return torch.empty_like(x)
+    qkv = linear(x.reshape(l0 * b1, e), in_proj_w, in_proj_b).reshape(l0, b1, 3 * e)
+    att = axis0_attention_wide(qkv, heads)
+    return linear(att.reshape(l0 * b1, e), out_proj_w, out_proj_b).reshape(l0, b1, e)
+
+
+def mins_check_widths(d: int, f: int, c: int) -> None:
+    """As in the reference only num_filters == news_embedding_dim can run: its chunk width D / C is not the GRU's input width F / C."""
+    if f != d:
+        raise RuntimeError(f"MINSUserEncoder: num_filters {f} != news_embedding_dim {d} — the attention's output is chunked into "
+                           f"{c} channels of width {d // c}, which the GRU of input width {f // c} cannot read; only the reference's "
+                           f"num_filters == news_embedding_dim configuration can run")
+
+
+def _mins_operands(x: Tensor, params: Sequence[Tensor], channels: int):
+    """x [B, S, D] and the eight tensors named by ``MINS_PARAMS``; refuses num_filters != news_embedding_dim as the reference's
+    forward does (its chunk of width D / C is not the GRU's input width F / C)."""
+    if len(params) != len(MINS_PARAMS):
+        raise ValueError(f"mins_user: {len(MINS_PARAMS)} parameters expected ({', '.join(MINS_PARAMS)})")
+    x = _dev(x, torch.float32, "clicked_news_vector")
+    c = int(channels)
+    if x.dim() != 3 or c < 1 or x.shape[2] % c:
+        raise ValueError(f"mins_user: clicked_news_vector {tuple(x.shape)} must be [B, S, D] with D a multiple of the {channels} channels")
+    mins_check_widths(x.shape[2], c * params[4].shape[1], c)
+    return x.contiguous(), c
+
+
+def mins_user(x: Tensor, lengths: Tensor, params: Sequence[Tensor], channels: int) -> Tensor:
+    """MINSUserEncoder.forward in eval() (reference user_encoder.py:211-243): x [B, S, D] clicked news, lengths int64 [B],
+    ``params`` the eight tensors named by ``MINS_PARAMS`` -> [B, D].  The attention (heads = channels) runs ACROSS THE B USERS at each
+    history slot, unmasked, as in the reference; head dims 65 .. 128 take ``mha_axis0_wide``, 1 .. 64 ``mha_axis0_any``.  The final
+    additive pooler over a sequence of one slot is the identity and is not run."""
+    x, c = _mins_operands(x, params, channels)
+    mha = mha_axis0_wide if x.shape[2] // c >= AXIS0_WIDE_MIN_DH else mha_axis0_any
+    return channel_gru_last_hidden(mha(x, *params[:4], c), lengths, *params[4:], c)
+
+
 class HalfTable:
     """IEEE-half copy of a news-embedding table for the scorer: ``rows`` float16 [n, D] and, when centred, ``mean`` float32 [D]
     (rows = half(T - mean)); see ``table_to_f16``."""

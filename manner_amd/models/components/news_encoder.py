@@ -732,6 +732,43 @@ class CAUMNewsEncoder(nn.Module):
         return hip.linear(all_vectors, self.linear.weight.detach(), self.linear.bias.detach())
 
 
+class NAMLCategoryEncoder(nn.Module):
+    """reference news_encoder.py:174-192 (``install(baselines=("mins_plm",))`` / ``("naml_plm",)`` bind it): embedding (``padding_idx=0``)
+    -> Linear -> ReLU, every operator on the HIP kernels with its backward (under no_grad the same operators record nothing); f32 whatever
+    the autocast state.  Row 0 of the table receives no gradient."""
+
+    def __init__(self, num_categories: int, category_embedding_dim: int, category_output_dim: int) -> None:
+        super().__init__()
+        self.category_embedding = nn.Embedding(num_embeddings=num_categories, embedding_dim=category_embedding_dim, padding_idx=0)
+        self.linear = nn.Linear(category_embedding_dim, category_output_dim)
+
+    def forward(self, category: torch.Tensor) -> torch.Tensor:
+        emb = self.category_embedding
+        x = train.embedding(category, emb.weight, emb.padding_idx)
+        return train.relu(train.linear(x, self.linear.weight, self.linear.bias))
+
+
+class NAMLNewsEncoder(nn.Module):
+    """reference news_encoder.py:195-236 — the news encoder of the NAML-PLM and MINS-PLM baselines (``install(baselines=("naml_plm",))`` /
+    ``("mins_plm",)`` bind it): the PLMTextEncoder mirror below and the category encoder, stacked to [N, 2, D] and pooled by the
+    AdditiveAttention mirror over those two slots."""
+
+    def __init__(self, plm_model: str, frozen_layers: List[int], text_embedding_dim: int, num_attention_heads: int, query_vector_dim: int,
+                 dropout_probability: float, num_categories: int, category_embedding_dim: int) -> None:
+        super().__init__()
+        self.text_encoder = PLMTextEncoder(plm_model=plm_model, frozen_layers=frozen_layers, text_embedding_dim=text_embedding_dim,
+                                           num_attention_heads=num_attention_heads, query_vector_dim=query_vector_dim,
+                                           dropout_probability=dropout_probability)
+        self.category_encoder = NAMLCategoryEncoder(num_categories=num_categories, category_embedding_dim=category_embedding_dim,
+                                                    category_output_dim=text_embedding_dim)
+        self.additive_attention = AdditiveAttention(text_embedding_dim, query_vector_dim)
+
+    def forward(self, news: Dict[str, Any]) -> torch.Tensor:
+        text_vector = self.text_encoder(news["text"])
+        category_vector = self.category_encoder(news["category"])
+        return self.additive_attention(torch.stack([text_vector, category_vector], dim=1))      # a copy; its backward is a split
+
+
 class LSTURCategoryEncoder(nn.Module):
     """reference news_encoder.py:239-255 (``install(baselines=("lstur_plm",))`` binds it): an embedding lookup with ``padding_idx=0`` on the
     HIP embedding entry, forward and backward (row 0 receives no gradient; an id outside the table raises at the next status check)."""

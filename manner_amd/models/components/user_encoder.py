@@ -1,6 +1,7 @@
-"""NAMLUserEncoder / NRMSUserEncoder / LSTURUserEncoder / CAUMUserEncoder — mirror of reference
-manner/models/components/user_encoder.py:9-89, 92-178 (NAML: imported by the reference as ``UserEncoder``, cr_module.py:16; NRMS: the
-user encoder of the PLM baselines; LSTUR and CAUM: opt-in, ``install(baselines=("lstur_plm",))`` / ``("caum_plm",)``)."""
+"""NAMLUserEncoder / NRMSUserEncoder / LSTURUserEncoder / CAUMUserEncoder / MINSUserEncoder — mirror of reference
+manner/models/components/user_encoder.py:9-89, 92-178, 181-243 (NAML: imported by the reference as ``UserEncoder``, cr_module.py:16;
+NRMS: the user encoder of the PLM baselines; LSTUR, CAUM and MINS: opt-in, ``install(baselines=("lstur_plm",))`` / ``("caum_plm",)`` /
+``("mins_plm",)``)."""
 import torch
 import torch.nn as nn
 
@@ -128,3 +129,50 @@ class CAUMUserEncoder(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0
             return train.caum_user_scores(clicked_news_vector, cand_news_vector, self._params(), mha.num_heads, p=p, seed=seed)
         return hip.caum_user_scores(clicked_news_vector, cand_news_vector, [t.detach() for t in self._params()], mha.num_heads)
+
+
+class MINSUserEncoder(nn.Module):
+    """reference user_encoder.py:181-243 — MINS's multi-channel GRU user encoder (``install(baselines=("mins_plm",))`` binds it):
+    ``forward(clicked_news_vector [B, S, D], hist_size [B])`` -> [B, D].
+
+    Batch-faithful to the reference: its nn.MultiheadAttention (heads = channels, head dim D / C: 128 as shipped) is batch_first=False
+    but receives [B, S, D], so attention runs ACROSS THE B USERS OF THE CALL at each history slot, unmasked, zero-padded slots
+    included — d clicked_news_vector is therefore not zero past a user's ``hist_size``.  ``torch.chunk`` then gives C contiguous
+    channels of width D / C, every one through the SAME ``nn.GRU`` on ``pack_padded_sequence(hist_size, enforce_sorted=False)``;
+    ``last_hidden`` of the channels is concatenated.  Here that is one input projection and ONE launch for the whole recurrence of all
+    B C sequences (csrc/mins.hip: W_hh in registers, H <= 128); ``hist_size`` is read on the device, never copied to the host, and the
+    GRU never reads a slot past it.  The final AdditiveAttention runs over a sequence of ONE slot: the identity, bit for bit — it is not
+    run, and where a graph is recorded its three parameters receive exact-zero gradients, as the reference's do.
+
+    The parameters live in the reference's submodules (``multi_channel_gru.*`` aliases the one ``gru``), so the state-dict keys are the
+    reference's; none of their own forwards runs.  As in the reference only ``num_filters == news_embedding_dim`` can run: construction
+    stays legal, ``forward`` refuses.  f32 whatever the autocast state.  S <= 256, D / C <= 128; a length outside [1, S] raises at the
+    next ``hip.check_status()`` / status poll."""
+
+    def __init__(self, news_embedding_dim: int, query_vector_dim: int, num_filters: int, num_gru_channels: int) -> None:
+        super().__init__()
+        self.num_gru_channels = num_gru_channels
+        self.multihead_attention = nn.MultiheadAttention(embed_dim=news_embedding_dim, num_heads=num_gru_channels)
+        self.additive_attention = AdditiveAttention(input_dim=news_embedding_dim, query_dim=query_vector_dim)
+        assert num_filters % num_gru_channels == 0
+        self.gru = nn.GRU(int(num_filters / num_gru_channels), int(num_filters / num_gru_channels))
+        self.multi_channel_gru = nn.ModuleList([self.gru for _ in range(num_gru_channels)])
+
+    def _params(self):
+        mha, g = self.multihead_attention, self.gru
+        return [mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0]
+
+    def forward(self, clicked_news_vector: torch.Tensor, hist_size: torch.Tensor) -> torch.Tensor:
+        if self.multihead_attention.dropout != 0.0:
+            raise RuntimeError("attention-probability dropout inside nn.MultiheadAttention is not built (the reference uses 0)")
+        hip.mins_check_widths(clicked_news_vector.shape[-1], self.num_gru_channels * self.gru.input_size, self.num_gru_channels)
+        dev = clicked_news_vector.device
+        hip.status_poll(dev)
+        if _differentiable(self, clicked_news_vector):
+            pool = self.additive_attention
+            out = train.mins_user(clicked_news_vector, hist_size, self._params(), self.num_gru_channels,
+                                  pool=[pool.query, pool.linear.weight, pool.linear.bias])
+        else:
+            out = hip.mins_user(clicked_news_vector, hist_size, [t.detach() for t in self._params()], self.num_gru_channels)
+        hip.status_arm(dev)
+        return out

@@ -9,6 +9,7 @@ with the HIP operator classes installed, without editing a line of the reference
     PYTHONPATH=<this repository> python -m manner_amd.run --baselines miner manner/train.py experiment=miner_weighted_mind
     PYTHONPATH=<this repository> python -m manner_amd.run --baselines caum_plm manner/train.py experiment=caum_plm_mind
     PYTHONPATH=<this repository> python -m manner_amd.run --baselines lstur_plm manner/train.py experiment=lstur_ini_mind
+    PYTHONPATH=<this repository> python -m manner_amd.run --baselines mins_plm manner/train.py experiment=mins_mind
 
 ``install()`` runs first (manner_amd/binding.py), then the script runs as ``__main__`` with ``sys.argv`` shifted, exactly as
 ``python <script.py> [args…]`` would (the script's directory is put first on ``sys.path`` as the interpreter does; the current

@@ -785,6 +785,97 @@ def lstur_user(user: Tensor, x: Tensor, lengths: Tensor, params: Sequence[Tensor
     return _LsturUser.apply(user, x, lengths, opts, table, *gru)
 
 
+class _ChannelGru(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, lengths: Tensor, dims, *params: Tensor):
+        out, ctx.saved_buf, ctx.saved_bytes = hip._channel_gru_forward(x, lengths, [t.detach() for t in params], dims, save=True)
+        ctx.dims = dims
+        ctx.save_for_backward(lengths, params[0], params[1])
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        lengths, w_ih, w_hh = ctx.saved_tensors
+        b, s, c, i, h = dims = ctx.dims
+        dev = ctx.saved_buf.device
+        lib = _lib.load()
+        g = _f32(g, "grad")
+        dx = torch.empty((b, s, c * i), dtype=torch.float32, device=dev)
+        grads = [torch.empty((3 * h, i), dtype=torch.float32, device=dev), torch.empty((3 * h, h), dtype=torch.float32, device=dev),
+                 torch.empty(3 * h, dtype=torch.float32, device=dev), torch.empty(3 * h, dtype=torch.float32, device=dev)]
+        with torch.cuda.device(dev):
+            need = int(lib.manner_hip_channel_gru_workspace_bytes(*dims))
+            ws = hip._workspace(need, dev)
+            _lib.check(lib.manner_hip_channel_gru_backward(hip._ptr(w_ih), hip._ptr(w_hh), hip._ptr(lengths), hip._ptr(g), c * h, *dims,
+                                                           hip._ptr(ctx.saved_buf), ctx.saved_bytes, hip._ptr(dx), *[hip._ptr(t) for t in grads],
+                                                           hip._ptr(ws), need, hip._stream()))
+        return (dx, None, None, *grads)
+
+
+def channel_gru_last_hidden(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, channels: int) -> Tensor:
+    """``hip.channel_gru_last_hidden`` with autograd into x and the four shared ``nn.GRU`` tensors: the forward keeps the gates of every
+    step, the backward is one launch walking the steps in reverse and the weight gradients over the rows stacked in (b, t, c) order — one
+    fixed-order sum over all channels.  d x is exactly 0 at the slots past a row's length."""
+    x, lengths, params, dims = hip._channel_gru_operands(x, lengths, w_ih, w_hh, b_ih, b_hh, channels)
+    return _ChannelGru.apply(x, lengths, dims, *params)
+
+
+class _Axis0AttentionWide(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv: Tensor, heads: int):
+        l0, b1, _ = qkv.shape
+        stats = torch.empty(l0 * b1 * heads * 3, dtype=torch.float32, device=qkv.device)
+        out = hip.axis0_attention_wide(qkv, heads, stats)
+        ctx.save_for_backward(qkv, out, stats)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        qkv, out, stats = ctx.saved_tensors
+        l0, b1, e3 = qkv.shape
+        dqkv = torch.empty_like(qkv)
+        lib = _lib.load()
+        with torch.cuda.device(qkv.device):
+            g = _f32(g, "grad")
+            _lib.check(lib.manner_hip_axis0_attention_wide_backward_q(hip._ptr(qkv), hip._ptr(out), hip._ptr(g), l0, b1, e3 // 3, ctx.heads,
+                                                                      hip._ptr(dqkv), hip._ptr(stats), hip._stream()))
+            _lib.check(lib.manner_hip_axis0_attention_wide_backward_kv(hip._ptr(qkv), hip._ptr(g), hip._ptr(stats), l0, b1, e3 // 3, ctx.heads,
+                                                                       hip._ptr(dqkv), hip._stream()))
+        return dqkv, None
+
+
+def mha_axis0_wide(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    """``mha_axis0_any`` at head dims 65 .. 128, with autograd (MINS's user encoder: head dim 128)."""
+    qkv = linear(x, in_proj_w, in_proj_b)
+    return linear(_Axis0AttentionWide.apply(qkv.contiguous(), int(heads)), out_proj_w, out_proj_b)
+
+
+class _UnitPool(torch.autograd.Function):
+    """AdditiveAttention over a sequence of ONE slot: the softmax over one logit is 1, so the output is the input bit for bit and the
+    pooler's three parameters receive exact zeros — as tensors, not None, as the reference's autograd gives them."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, *pool: Tensor):
+        ctx.save_for_backward(*pool)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return (g, *[torch.zeros_like(t) if need else None for t, need in zip(ctx.saved_tensors, ctx.needs_input_grad[1:])])
+
+
+def mins_user(x: Tensor, lengths: Tensor, params: Sequence[Tensor], channels: int, pool: Sequence[Tensor] = ()) -> Tensor:
+    """MINSUserEncoder.forward (user_encoder.py:211-243) with autograd into x and the eight parameters (``hip.MINS_PARAMS`` order):
+    x [B, S, D], lengths int64 [B] (never copied to the host) -> [B, D].  d x is NOT zero at the slots past a user's length: the
+    attention reads them on behalf of the other users; only the GRU's own input gradient is zero there.  ``pool``: the parameters of
+    the final AdditiveAttention, which runs over one slot and is the identity — they receive exact-zero gradients."""
+    x, c = hip._mins_operands(x, params, channels)
+    mha = mha_axis0_wide if x.shape[2] // c >= hip.AXIS0_WIDE_MIN_DH else mha_axis0_any
+    out = channel_gru_last_hidden(mha(x, *params[:4], c), lengths, *params[4:], c)
+    return _UnitPool.apply(out, *pool) if pool else out
+
+
 class _LinearTanh(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, weight: Tensor, bias: Optional[Tensor]):
