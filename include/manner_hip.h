@@ -690,6 +690,18 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
                                   int32_t H1, int32_t H2, int32_t heads, float p, uint64_t seed, uint32_t site0, void* saved, size_t saved_bytes,
                                   float* grad_x, float* grad_c, float* const* grads, void* workspace, size_t workspace_bytes,
                                   manner_hip_stream_t stream);
+/* manner_hip_caum_scores_all is the candidate loop of CAUMPLMModule.forward (baselines/caum_plm_module.py:159-161) in one call, forward
+ * only and without dropout (eval()): x [B, S, D], cand contiguous [B, C, D], the same 16 params -> out [B, C] with out[b, c] what
+ * manner_hip_caum_user_forward returns for the column cand[:, c, :].  Every product whose operand depends on (b, s) alone or on (b, c)
+ * alone is taken once; only attention -> linear3 -> the two tanh layers run over the B C S rows.  Those rows live in `workspace`, and the
+ * entry walks the columns in passes of as many as `workspace_bytes` holds (_workspace_bytes(..., cols_per_pass) gives the bytes for a
+ * pass width; the least workspace holds one column).  A column's bits do not depend on the pass width.  Limits and messages as
+ * manner_hip_caum_user_forward; C == 0 or B == 0 writes nothing; C < 0 is MANNER_HIP_E_INVALID. */
+size_t manner_hip_caum_scores_all_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads,
+                                                  int64_t cols_per_pass);
+int manner_hip_caum_scores_all(const float* x, const float* cand, const float* const* params, int64_t B, int64_t S, int64_t C, int32_t D, int32_t F,
+                               int32_t U, int32_t H1, int32_t H2, int32_t heads, float* out, void* workspace, size_t workspace_bytes,
+                               manner_hip_stream_t stream);
 /* DenseAttention alone (attention.py:134-141): y [R, O] = tanh(x W^T + b), and grad_pre = grad_out (1 - y^2) for its backward */
 int manner_hip_linear_tanh(const float* x, const float* weight, const float* bias, int64_t R, int32_t K, int32_t O, float* y,
                            manner_hip_stream_t stream);

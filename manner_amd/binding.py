@@ -37,7 +37,8 @@ of the CAUM baseline (baselines/caum_plm_module.py:15-16 imports ``CAUMNewsEncod
     user_encoder      CAUMUserEncoder
     attention         DenseAttention
 
-``CAUMPLMModule``'s own lines — the per-candidate loop, ``to_dense_batch``, the loss, the metrics — stay the reference's torch.
+``CAUMPLMModule``'s own lines — the per-candidate loop, ``to_dense_batch``, the loss, the metrics — stay the reference's torch
+(``hotpath.caum_forward`` is its ``forward`` with the loop as one call, for a module that chooses to delegate: INTEGRATION §4).
 
 ``install(baselines=("lstur_plm",))`` (configs/model/lstur_plm.yaml; the experiments lstur_{ini,con}_{mind,adressa}) rebinds the three
 leaf classes of the LSTUR baseline (baselines/lstur_plm_module.py imports ``LSTURNewsEncoder`` and ``LSTURUserEncoder``; the news

@@ -7,7 +7,9 @@
 // producers of cat[cnn, self] write into the two column ranges of one buffer, and the candidate half of the dense attention's first
 // Linear is computed once per user.  nn.MultiheadAttention is batch_first=False but fed [B, S, U]: attention runs ACROSS THE B USERS
 // of the call at each history slot (as in the reference's other batch_first=False calls), so B is the key axis.
-// The workload is small (B = 8, S = 50, widths 400) and latency-bound: plain f32 VALU kernels.  Every reduction across rows runs in a
+// manner_hip_caum_scores_all (the last section) scores ALL candidate columns of a dense [B, C, D] tensor in one call, eval() only, on
+// shared history products and an f32 MFMA linear.
+// The per-column workload is small (B = 8, S = 50, widths 400) and latency-bound: plain f32 VALU kernels.  Every reduction across rows runs in a
 // fixed order (no floating-point atomics): two runs give the same bits.
 #include <math.h>
 
@@ -700,6 +702,273 @@ void plan_work(Bump& b, Work& w, const Dims& m) {
   w.part = b.take((size_t)wgrad_groups(m.R) * ok);
 }
 
+// ---------------------------------------------------------------- all candidates of a call on shared history products
+// Every nn.Linear of CAUMUserEncoder.forward in front of a nonlinearity acts on a history-only operand plus a candidate-only operand
+// (eval(): no dropout between them), so with b the user, s the slot, c the candidate column
+//   q|k|v[b, c, s] = QH[b, s] + QC[b, c],  all[b, c, s] = M att[b, c, s] + A[b, s] + Bc[b, c],  pre[b, c, s] = Wa[:, :U] all[b, c, s] + CT[b, c]
+// (M = W3[:, F:] Wout folded once per call; manner_hip_caum_scores_all below lists the terms).  Only att -> all -> t1 -> t2 run over the
+// B C S wide rows, in (b, c, s) order so that score_kernel / user_kernel take (b, c) as B C pseudo-users.
+constexpr int WL_BK = 32;                            // input features per staging of the row-tiled linear
+constexpr int WL_LD = WL_BK + 1;                     // LDS row pitch in floats: odd, so that the rows of an MFMA operand read distinct banks
+constexpr int WL_SMALL_ROWS = 1024;                  // fewer rows than this: the 32 x 32 tile (more workgroups), else 128 x 64
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// where row r of a pass sits: r = (b * cp + cl) * S + s with cl the column within the pass, c = c0 + cl the column of the call
+struct RowMap { int S, cp, C, c0; };
+
+// y[r, o] = act(bias[o] + add_bs[b S + s, o] + add_bc[b C + c, o] + sum_k x[r, k] W[o, k]) — each of the three terms may be NULL; x rows
+// ldx apart, W rows ldw apart, y rows ldy apart.  True f32 on the matrix cores, in two tiles:
+//   128 rows x 64 output features, grid (ceil(R / 128), ceil(O / 64)): each wave takes 32 rows x 64 features on v_mfma_f32_32x32x2_f32;
+//   SMALL, 32 x 32, grid (ceil(R / 32), ceil(O / 32)): each wave takes a 16 x 16 quarter on v_mfma_f32_16x16x4_f32 — for the launches of a
+//     few hundred rows (the history side and the candidate side at B = 8), which the large tile leaves on a few dozen workgroups.
+// Either way a workgroup stages its rows and weight rows per 32 input features (the next step's floats wait in registers while this
+// one multiplies), and an output is one k-ascending fmaf chain whatever its place in a tile and whichever tile: a row's bits do not
+// depend on the tile, the pass or the row count of the launch.
+template <bool TANH, bool SMALL>
+__global__ __launch_bounds__(CA_BLOCK) void wlin_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ W, int ldw,
+                                                   const float* __restrict__ bias, const float* __restrict__ add_bs,
+                                                   const float* __restrict__ add_bc, RowMap m, int64_t R, int K, int O, float* __restrict__ y, int ldy) {
+  constexpr int BM = SMALL ? 32 : 128, BN = SMALL ? 32 : 64;
+  constexpr int SROWS = CA_BLOCK / WL_BK, XV = BM / SROWS, WV = BN / SROWS;        // staging: 8 rows per sweep; floats per thread of x, of W
+  __shared__ float xs[BM][WL_LD];
+  __shared__ float ws[BN][WL_LD];
+  const int tid = threadIdx.x, wave = tid / CA_WAVE, lane = tid % CA_WAVE;
+  const int64_t r0 = (int64_t)blockIdx.x * BM;
+  const int nr = (int)min((int64_t)BM, R - r0);
+  const int o0 = blockIdx.y * BN;
+  const int sk = tid % WL_BK, sr = tid / WL_BK;          // staging: thread = (input feature, row)
+  float xv[XV], wv[WV];
+  auto fetch = [&](int k0) {
+    const bool kin = k0 + sk < K;
+#pragma unroll
+    for (int i = 0; i < XV; ++i) {
+      const int rr = sr + i * SROWS;
+      xv[i] = (kin && rr < nr) ? x[(size_t)(r0 + rr) * ldx + k0 + sk] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < WV; ++i) {
+      const int oo = sr + i * SROWS;
+      wv[i] = (kin && o0 + oo < O) ? W[(size_t)(o0 + oo) * ldw + k0 + sk] : 0.f;          // past O or K: zeros, no branch below
+    }
+  };
+  // one output: the epilogue terms in a fixed order
+  auto emit = [&](int rr, int oo, float v) {
+    const int o = o0 + oo;
+    if (rr >= nr || o >= O) return;
+    const int64_t r = r0 + rr;
+    if (bias) v += bias[o];
+    if (add_bs || add_bc) {                              // r < 2^31 (caum_all_check)
+      const uint32_t pu = (uint32_t)r / (uint32_t)m.S, s = (uint32_t)r - pu * (uint32_t)m.S;
+      const uint32_t b = pu / (uint32_t)m.cp, cl = pu - b * (uint32_t)m.cp;
+      if (add_bs) v += add_bs[((size_t)b * m.S + s) * O + o];
+      if (add_bc) v += add_bc[((size_t)b * m.C + m.c0 + cl) * O + o];
+    }
+    y[(size_t)r * ldy + o] = TANH ? tanhf(v) : v;
+  };
+  f32x16 acc0, acc1;
+  f32x4 accs;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) accs[i] = 0.f;
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += WL_BK) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < XV; ++i) xs[sr + i * SROWS][sk] = xv[i];
+#pragma unroll
+    for (int i = 0; i < WV; ++i) ws[sr + i * SROWS][sk] = wv[i];
+    __syncthreads();
+    if (k0 + WL_BK < K) fetch(k0 + WL_BK);
+    if constexpr (SMALL) {                               // operand maps: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15]
+      const int ar = (wave >> 1) * 16 + (lane & 15), br = (wave & 1) * 16 + (lane & 15), kq = lane >> 4;
+#pragma unroll
+      for (int kk = 0; kk < WL_BK; kk += 4) accs = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[ar][kk + kq], ws[br][kk + kq], accs, 0, 0, 0);
+    } else {                                             // A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
+      const int ar = wave * 32 + (lane & 31), kh = lane >> 5;
+#pragma unroll
+      for (int kk = 0; kk < WL_BK; kk += 2) {
+        const float a = xs[ar][kk + kh];
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, ws[lane & 31][kk + kh], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, ws[32 + (lane & 31)][kk + kh], acc1, 0, 0, 0);
+      }
+    }
+  }
+  if constexpr (SMALL) {                                 // C / D map: column = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) emit((wave >> 1) * 16 + 4 * (lane >> 4) + reg, (wave & 1) * 16 + (lane & 15), accs[reg]);
+  } else {                                               // C / D map: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int rr = wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+      emit(rr, lane & 31, acc0[reg]);
+      emit(rr, 32 + (lane & 31), acc1[reg]);
+    }
+  }
+}
+int launch_wlin(bool tanh_act, const float* x, int ldx, const float* W, int ldw, const float* bias, const float* add_bs, const float* add_bc, RowMap m,
+                int64_t R, int K, int O, float* y, int ldy, hipStream_t s) {
+  const bool small = R < WL_SMALL_ROWS;
+  const int bm = small ? 32 : 128, bn = small ? 32 : 64;
+  const dim3 g((unsigned)((R + bm - 1) / bm), (unsigned)((O + bn - 1) / bn));
+#define MANNER_WLIN(T_, S_) hipLaunchKernelGGL((wlin_kernel<T_, S_>), g, dim3(CA_BLOCK), 0, s, x, ldx, W, ldw, bias, add_bs, add_bc, m, R, K, O, y, ldy)
+  if (tanh_act && small) MANNER_WLIN(true, true);
+  else if (tanh_act) MANNER_WLIN(true, false);
+  else if (small) MANNER_WLIN(false, true);
+  else MANNER_WLIN(false, false);
+#undef MANNER_WLIN
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+// a0any_fwd_kernel with q, k, v of the pair (e = cl S + s, head) formed on the way into registers and LDS: row n is
+// QH[n, s] + QC[n, c0 + cl] (qh [N, S, 3D], qc [N, C, 3D]); out [(n cp + cl) S + s, D].  The [N, C, S, 3D] tensor is never written.
+template <int DHP>
+__global__ __launch_bounds__(CA_BLOCK) void a0sum_fwd_kernel(const float* __restrict__ qh, const float* __restrict__ qc, float* __restrict__ out, int64_t N,
+                                                        RowMap m, int D, int heads, int dh, A0Plan pl) {
+  __shared__ float ks[CA_LDS], vs[CA_LDS];
+  const int E = m.cp * m.S;
+  const A0Thread t = a0_thread(pl, N, E, heads);
+  const float scale = 1.0f / sqrtf((float)dh);
+  const size_t ldh = (size_t)m.S * 3 * D, ldc = (size_t)m.C * 3 * D;
+  const int cl = t.e / m.S, sl = t.e - cl * m.S;
+  const float* hb = qh + (size_t)t.n * ldh + (size_t)sl * 3 * D + t.hh * dh;
+  const float* cb = qc + (size_t)t.n * ldc + (size_t)(m.c0 + cl) * 3 * D + t.hh * dh;
+  float q[DHP], o[DHP];
+#pragma unroll
+  for (int d = 0; d < DHP; ++d) { q[d] = (t.act && d < dh) ? (hb[d] + cb[d]) * scale : 0.f; o[d] = 0.f; }
+  float mx = -INFINITY, sum = 0.f;
+  for (int64_t t0 = 0; t0 < N; t0 += pl.KT) {
+    const int cnt = (int)min((int64_t)pl.KT, N - t0);
+    auto row = [&](int third, int j, int e, int hh, int d) {
+      const int c = e / m.S, s = e - c * m.S;
+      const size_t at = (size_t)third * D + hh * dh + d;
+      return qh[(t0 + j) * ldh + (size_t)s * 3 * D + at] + qc[(t0 + j) * ldc + (size_t)(m.c0 + c) * 3 * D + at];
+    };
+    __syncthreads();
+    a0_stage(pl, cnt, dh, E, heads, ks, vs, [&](int j, int e, int hh, int d) { return row(1, j, e, hh, d); },
+             [&](int j, int e, int hh, int d) { return row(2, j, e, hh, d); });
+    __syncthreads();
+    if (t.act)
+      for (int j = 0; j < cnt; ++j) {
+        const float* kp = ks + (t.pl * pl.KT + j) * dh;
+        const float* vp = vs + (t.pl * pl.KT + j) * dh;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) s = fmaf(q[d], kp[d], s);
+        if (s > mx) {
+          const float f = expf(mx - s);
+          sum *= f;
+#pragma unroll
+          for (int d = 0; d < DHP; ++d) o[d] *= f;
+          mx = s;
+        }
+        const float p = expf(s - mx);
+        sum += p;
+#pragma unroll
+        for (int d = 0; d < DHP; ++d)
+          if (d < dh) o[d] = fmaf(p, vp[d], o[d]);
+      }
+  }
+  if (t.act) {
+    const float inv = 1.0f / sum;
+    float* dst = out + (((size_t)t.n * m.cp + cl) * m.S + sl) * D + t.hh * dh;
+#pragma unroll
+    for (int d = 0; d < DHP; ++d)
+      if (d < dh) dst[d] = o[d] * inv;
+  }
+}
+int launch_a0sum_fwd(const float* qh, const float* qc, float* out, int64_t N, RowMap m, int D, int heads, hipStream_t s) {
+  const int dh = D / heads;
+  const A0Plan pl = a0_plan(N, dh);
+  const int64_t pairs = (int64_t)m.cp * m.S * heads;
+  const dim3 g((unsigned)((pairs + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0sum_fwd_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qh, qc, out, N, m, D, heads, dh, pl)
+  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+#undef MANNER_A0
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+// grid (B S): win[r] = [x[b, s-1], x[b, s], x[b, s+1]] (circular, user_encoder.py:128-144) — the history three quarters of linear1's operand
+__global__ __launch_bounds__(CA_BLOCK) void window_kernel(const float* __restrict__ x, int S, int D, float* __restrict__ win) {
+  const int64_t r = blockIdx.x, b = r / S;
+  const int s = (int)(r - b * S);
+  const int sl = s == 0 ? S - 1 : s - 1, sr = s == S - 1 ? 0 : s + 1;
+  const float* xb = x + (size_t)b * S * D;
+  float* p = win + (size_t)r * 3 * D;
+  for (int d = threadIdx.x; d < D; d += CA_BLOCK) {
+    p[d] = xb[(size_t)sl * D + d]; p[D + d] = xb[(size_t)s * D + d]; p[2 * D + d] = xb[(size_t)sr * D + d];
+  }
+}
+// out[k, j] = in[j, k], in [n, n] (out_proj.weight, for the fold W3[:, F:] Wout as a row-times-row product)
+__global__ __launch_bounds__(CA_BLOCK) void transpose_kernel(const float* __restrict__ in, int n, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x;
+  if (i >= (int64_t)n * n) return;
+  const int k = (int)(i / n), j = (int)(i - (int64_t)k * n);
+  out[i] = in[(size_t)j * n + k];
+}
+
+// dst[h, j] = src[h, j], j < width, rows dpitch / spitch floats apart: the candidate rows of a pass out of [B, C, D], its scores into [B, C]
+__global__ __launch_bounds__(CA_BLOCK) void rows_copy_kernel(const float* __restrict__ src, int64_t spitch, float* __restrict__ dst, int64_t dpitch,
+                                                        int64_t width, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * CA_BLOCK) {
+    const int64_t h = i / width, j = i - h * width;
+    dst[h * dpitch + j] = src[h * spitch + j];
+  }
+}
+
+// the buffers of one call: what depends on (b, s) alone, on (b, c) alone, on the weights alone — taken once — and the wide rows of a pass
+struct AllBufs {
+  float *win, *wx, *hx, *qh, *a, *cx1, *cx2, *qc, *bcand, *ct, *owt, *fold, *ba;      // once per call
+  float *att, *all, *t1, *t2, *score, *g, *cd, *outp;                                    // per pass of cp columns
+};
+void plan_all(Bump& b, AllBufs& w, const Dims& m, int64_t C, int64_t cp) {
+  const size_t R = (size_t)m.R, N = (size_t)m.B * C, P = (size_t)m.B * cp, W = P * m.S;
+  w.win = b.take(R * 3 * m.D);
+  w.wx = b.take(R * m.F);
+  w.hx = b.take(R * m.U);
+  w.qh = b.take(R * 3 * m.U);
+  w.a = b.take(R * m.U);
+  w.cx1 = b.take(N * m.F);
+  w.cx2 = b.take(N * m.U);
+  w.qc = b.take(N * 3 * m.U);
+  w.bcand = b.take(N * m.U);
+  w.ct = b.take(N * m.H1);
+  w.owt = b.take((size_t)m.U * m.U);
+  w.fold = b.take((size_t)m.U * m.U);
+  w.ba = b.take(m.U);
+  w.att = b.take(W * m.U);
+  w.all = b.take(W * m.U);
+  w.t1 = b.take(W * m.H1);
+  w.t2 = b.take(W * m.H2);
+  w.score = b.take(W);
+  w.g = b.take(W);
+  w.cd = b.take(P * m.D);
+  w.outp = b.take(P);
+}
+size_t all_bytes(const Dims& m, int64_t C, int64_t cp) {
+  Bump b(nullptr);
+  AllBufs w;
+  plan_all(b, w, m, C, cp);
+  return b.off * sizeof(float) + 256;
+}
+// most columns a pass may take: its rows and its (column, slot, head) pairs stay below 2^31
+int64_t all_max_cols(const Dims& m, int64_t C) {
+  const int64_t lim = 0x7fffffffll / (std::max<int64_t>(m.B, m.heads) * m.S);
+  return std::max<int64_t>(1, std::min(C, lim));
+}
+int caum_all_check(const char* who, int64_t B, int64_t S, int64_t C, int D, int F, int U, int H1, int H2, int heads, Dims& m) {
+  int rc;
+  if ((rc = caum_check(who, B, S, D, F, U, H1, H2, heads, m))) return rc;
+  if (C < 0) return fail(MANNER_HIP_E_INVALID, "%s: bad shape C=%lld", who, (long long)C);
+  if (B * std::max<int64_t>(C, 1) > 0x7fffffffll || std::max<int64_t>(B, heads) * S > 0x7fffffffll)
+    return fail(MANNER_HIP_E_INVALID, "%s: B*C or one column's rows exceed the grid", who);
+  return MANNER_HIP_OK;
+}
+
 }  // namespace
 }  // namespace manner
 
@@ -919,6 +1188,88 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
   hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((D + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.da1, 4 * D, 3 * D, w.da2,
                      2 * D, w.dcd, Si, D, d1, true, grad_c);
   MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+size_t manner_hip_caum_scores_all_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads,
+                                                  int64_t cols_per_pass) {
+  if (B <= 0 || S <= 0 || C <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0 || cols_per_pass <= 0) return 0;
+  const Dims m{B, S, B * S, D, F, U, H1, H2, heads};
+  return all_bytes(m, C, std::min(cols_per_pass, all_max_cols(m, C)));
+}
+
+// CAUMPLMModule.forward's candidate loop in one call, eval(): out[b, c] = CAUMUserEncoder.forward(x, cand[:, c, :])[b].
+//   once over the B S rows:  WX = W1[:, :3D] window + b1, HX = W2[:, D:] x + b2, QH = Win HX + bin, A = W3[:, :F] WX + (W3[:, F:] bout + b3)
+//   once over the B C rows:  CX1 = W1[:, 3D:] c, CX2 = W2[:, :D] c, QC = Win CX2, Bc = W3[:, :F] CX1, CT = Wa[:, U:] c + ba
+//   once per call:           M = W3[:, F:] Wout
+//   per pass of columns, over its B cp S rows: att (q | k | v = QH + QC), all = M att + A + Bc, t1 = tanh(Wa[:, :U] all + CT),
+//   t2 = tanh(Wb t1 + bb), then score_kernel / user_kernel with (b, c) as pseudo-users.
+// The columns per pass follow from workspace_bytes; a column's bits do not depend on it.
+int manner_hip_caum_scores_all(const float* x, const float* cand, const float* const* params, int64_t B, int64_t S, int64_t C, int32_t D, int32_t F,
+                               int32_t U, int32_t H1, int32_t H2, int32_t heads, float* out, void* workspace, size_t workspace_bytes,
+                               manner_hip_stream_t stream) {
+  int rc;
+  Dims m;
+  if ((rc = caum_all_check("caum_scores_all", B, S, C, D, F, U, H1, H2, heads, m))) return rc;
+  if (B == 0 || C == 0) return MANNER_HIP_OK;
+  if (!x || !cand || !params || !out || !workspace) return fail(MANNER_HIP_E_INVALID, "caum_scores_all: null pointer");
+  for (int i = 0; i < P_COUNT; ++i)
+    if (!params[i]) return fail(MANNER_HIP_E_INVALID, "caum_scores_all: null parameter %d", i);
+  if (workspace_bytes < all_bytes(m, C, 1))
+    return fail(MANNER_HIP_E_WORKSPACE, "caum_scores_all: workspace too small (%zu bytes hold one column)", all_bytes(m, C, 1));
+  int64_t cp = 1, hi = all_max_cols(m, C);                 // the most columns whose wide rows fit
+  while (cp < hi) {
+    const int64_t mid = (cp + hi + 1) / 2;
+    if (all_bytes(m, C, mid) <= workspace_bytes) cp = mid; else hi = mid - 1;
+  }
+  const int64_t passes = (C + cp - 1) / cp;
+  cp = (C + passes - 1) / passes;                          // as many passes, of even width (no last pass of one column)
+  hipStream_t s = (hipStream_t)stream;
+  Bump bump(workspace);
+  AllBufs w;
+  plan_all(bump, w, m, C, cp);
+  const int64_t R = m.R, N = B * C;
+  const int FU = F + U, Si = (int)S;
+  const RowMap flat{1, 1, 1, 0};
+  const float* const none = nullptr;
+  hipLaunchKernelGGL(window_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, x, Si, D, w.win);
+  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_wlin(false, w.win, 3 * D, params[P_W1], 4 * D, params[P_B1], none, none, flat, R, 3 * D, F, w.wx, F, s))) return rc;
+  if ((rc = launch_wlin(false, x, D, params[P_W2] + D, 2 * D, params[P_B2], none, none, flat, R, D, U, w.hx, U, s))) return rc;
+  if ((rc = launch_wlin(false, w.hx, U, params[P_WIN], U, params[P_BIN], none, none, flat, R, U, 3 * U, w.qh, 3 * U, s))) return rc;
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)U * U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, params[P_WOUT], U, w.owt);
+  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_wlin(false, params[P_W3] + F, FU, w.owt, U, none, none, none, flat, U, U, U, w.fold, U, s))) return rc;
+  if ((rc = launch_wlin(false, params[P_BOUT], U, params[P_W3] + F, FU, params[P_B3], none, none, flat, 1, U, U, w.ba, U, s))) return rc;
+  if ((rc = launch_wlin(false, w.wx, F, params[P_W3], FU, w.ba, none, none, flat, R, F, U, w.a, U, s))) return rc;
+  if ((rc = launch_wlin(false, cand, D, params[P_W1] + 3 * D, 4 * D, none, none, none, flat, N, D, F, w.cx1, F, s))) return rc;
+  if ((rc = launch_wlin(false, cand, D, params[P_W2], 2 * D, none, none, none, flat, N, D, U, w.cx2, U, s))) return rc;
+  if ((rc = launch_wlin(false, w.cx2, U, params[P_WIN], U, none, none, none, flat, N, U, 3 * U, w.qc, 3 * U, s))) return rc;
+  if ((rc = launch_wlin(false, w.cx1, F, params[P_W3], FU, none, none, none, flat, N, F, U, w.bcand, U, s))) return rc;
+  if ((rc = launch_wlin(false, cand, D, params[P_WA] + U, 2 * U, params[P_BA], none, none, flat, N, D, H1, w.ct, H1, s))) return rc;
+  for (int64_t c0 = 0; c0 < C; c0 += cp) {
+    const int64_t n = std::min(cp, C - c0), P = B * n, rows = P * S;
+    const RowMap rm{Si, (int)n, (int)C, (int)c0};
+    if ((rc = launch_a0sum_fwd(w.qh, w.qc, w.att, B, rm, U, heads, s))) return rc;
+    if ((rc = launch_wlin(false, w.att, U, w.fold, U, none, w.a, w.bcand, rm, rows, U, U, w.all, U, s))) return rc;
+    if ((rc = launch_wlin(true, w.all, U, params[P_WA], 2 * U, none, none, w.ct, rm, rows, U, H1, w.t1, H1, s))) return rc;
+    if ((rc = launch_wlin(true, w.t1, H1, params[P_WB], H1, params[P_BB], none, none, rm, rows, H1, H2, w.t2, H2, s))) return rc;
+    const bool whole = n == C;
+    if (!whole) {
+      hipLaunchKernelGGL(rows_copy_kernel, dim3(flat_grid(P * D)), dim3(CA_BLOCK), 0, s, cand + c0 * D, C * D, w.cd, n * D, n * D, P * D);
+      MANNER_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(score_kernel, dim3((unsigned)((rows + CA_ROWS - 1) / CA_ROWS)), dim3(CA_BLOCK), 0, s, w.t2, params[P_WC], params[P_BC], w.all,
+                       whole ? cand : w.cd, rows, Si, H2, U, w.score, w.g);
+    MANNER_LAUNCH_CHECK();
+    hipLaunchKernelGGL(user_kernel, dim3((unsigned)((P + CA_WAVES - 1) / CA_WAVES)), dim3(CA_BLOCK), 0, s, w.score, w.g, P, Si, whole ? out : w.outp,
+                       (const float*)nullptr, (float*)nullptr, (float*)nullptr);
+    MANNER_LAUNCH_CHECK();
+    if (!whole) {
+      hipLaunchKernelGGL(rows_copy_kernel, dim3(flat_grid(P)), dim3(CA_BLOCK), 0, s, w.outp, n, out + c0, C, n, P);
+      MANNER_LAUNCH_CHECK();
+    }
+  }
   return MANNER_HIP_OK;
 }
 

@@ -881,6 +881,36 @@ def caum_user_scores(x: Tensor, c: Tensor, params: Sequence[Tensor], heads: int)
     return _caum_forward(x, c, params, dims, 0.0, 0, CAUM_DROPOUT_SITE)[0]
 
 
+#: default cap of ``caum_scores_all``'s workspace: 256 MiB hold every column of a MIND dev batch at B = 8 (C = 300 at the shipped widths:
+#: 0.7 MiB of wide rows per column and user) and 13 columns per pass at B = 64; what is taken once per call comes on top when it is more
+CAUM_ALL_WORKSPACE_BYTES = 256 << 20
+
+
+def caum_scores_all(x: Tensor, cand: Tensor, params: Sequence[Tensor], heads: int, max_workspace_bytes: Optional[int] = None) -> Tensor:
+    """The candidate loop of CAUMPLMModule.forward (reference baselines/caum_plm_module.py:159-161) in one library call, eval() only:
+    x [B, S, D] clicked news, cand [B, C, D] dense candidates, ``params`` as ``caum_user_scores`` -> scores [B, C] with column c what
+    ``caum_user_scores(x, cand[:, c, :], ...)`` gives.  The products that depend on the history alone or on the candidate alone are
+    taken once; only attention, linear3 and the dense attention's two tanh layers run over the B C S rows.  Those rows live in a
+    workspace of at most ``max_workspace_bytes`` (default ``CAUM_ALL_WORKSPACE_BYTES``; never less than one column needs) and the
+    library walks the columns in as many passes as that takes; a column's bits do not depend on the cap."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 3:
+        raise ValueError(f"caum_scores_all: cand_news_vector {tuple(getattr(cand, 'shape', ()))} must be [B, C, D]")
+    b, c = cand.shape[0], cand.shape[1]
+    x, _, params, dims = _caum_operands(x, cand[:, 0, :] if c else cand.new_empty((b, cand.shape[2])), params, heads)
+    cand = _dev(cand, torch.float32, "cand_news_vector").contiguous()
+    out = torch.empty((b, c), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    args = (dims[0], dims[1], c) + dims[2:]
+    with torch.cuda.device(x.device):
+        least, full = (int(lib.manner_hip_caum_scores_all_workspace_bytes(*args, n)) for n in (1, max(c, 1)))
+        cap = CAUM_ALL_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+        need = min(full, max(cap, least))
+        work = _workspace(need, x.device)
+        tab = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        _lib.check(lib.manner_hip_caum_scores_all(_ptr(x), _ptr(cand), tab, *args, _ptr(out), _ptr(work), need, _stream()))
+    return out
+
+
 def linear_tanh(x: Tensor, weight: Tensor, bias: Optional[Tensor]) -> Tensor:
     """tanh(nn.Linear(x)) in one kernel on f32 rows (DenseAttention, reference attention.py:135-138): x [R, K] -> [R, O]."""
     x = _dev(x, torch.float32, "input").contiguous()

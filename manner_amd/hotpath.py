@@ -84,6 +84,28 @@ def cr_forward(news_encoder, batch: Dict, late_fusion: bool = True, user_encoder
     return hip.to_dense(ragged, cand_off, _width(batch, "cand_max", cand_off)) if dense else ragged
 
 
+def caum_forward(news_encoder, user_encoder, batch: Dict, dense: bool = True) -> Tensor:
+    """CAUMPLMModule.forward (reference baselines/caum_plm_module.py:146-165): the two news-encoder calls, ``to_dense_batch`` of both
+    sides, and the candidate loop as ONE call of ``user_encoder.forward_all`` (the CAUMUserEncoder of this package) -> scores
+    [B, Cmax] with the reference's value in every slot: a zero-padded candidate row scores 0, a zero-padded history row takes part
+    in every user's softmax.  No host synchronisation when the batch carries ``hist_max`` / ``cand_max``.  ``dense=False`` returns
+    the real slots of that matrix as the ragged [sum c_i] vector (the padded rows still take part in the attention across the
+    users, as in the reference; the selection reads the count back to the host)."""
+    nb =batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    hist_vec = news_encoder(batch["x_hist"])
+    cand_vec = news_encoder(batch["x_cand"])
+    hist_off = segment_offsets(batch["batch_hist"], nb)
+    cand_off = segment_offsets(batch["batch_cand"], nb)
+    hist_dense = hip.to_dense(hist_vec, hist_off, _width(batch, "hist_max", hist_off))
+    cand_dense = hip.to_dense(cand_vec, cand_off, _width(batch, "cand_max", cand_off), with_mask=not dense)
+    if not dense:
+        cand_dense, real = cand_dense
+    scores = user_encoder.forward_all(hist_dense, cand_dense)
+    hip.status_arm(cand_vec.device)
+    return scores if dense else scores[real]
+
+
 def _cat_tokens(a: Dict, b: Dict, pad_id: int) -> Dict:
     """Two tokenised news sets as one call: rows of `a` then rows of `b`, right-padded to the longer padded length."""
     la, lb = a["input_ids"].shape[1], b["input_ids"].shape[1]

@@ -97,7 +97,8 @@ class CAUMUserEncoder(nn.Module):
     history slot, and the softmax over the history is unmasked (zero-padded slots take part).  ``DenseAttention(input_dim=2 U)`` is fed
     cat[all (U), candidate (D)]: as in the reference only D == U can run; construction stays legal, ``forward`` refuses D != U.
     f32 whatever the autocast state.  The three dropouts are on in train() only and draw one seed per call from torch's CPU generator
-    (sites 7, 8, 9 of the counter-based generator)."""
+    (sites 7, 8, 9 of the counter-based generator).  ``forward_all`` takes the whole dense candidate tensor [B, C, D]: at evaluation
+    time it is one library call for all C columns, otherwise the reference's loop over ``forward``."""
 
     def __init__(self, news_vector_dim: int, num_filters: int, dense_att_hidden_dim1: int, dense_att_hidden_dim2: int, user_vector_dim: int,
                  num_attention_heads: int, dropout_probability: float) -> None:
@@ -129,6 +130,27 @@ class CAUMUserEncoder(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0
             return train.caum_user_scores(clicked_news_vector, cand_news_vector, self._params(), mha.num_heads, p=p, seed=seed)
         return hip.caum_user_scores(clicked_news_vector, cand_news_vector, [t.detach() for t in self._params()], mha.num_heads)
+
+    def forward_all(self, clicked_news_vector: torch.Tensor, cand_news_vector: torch.Tensor) -> torch.Tensor:
+        """The candidate loop of CAUMPLMModule.forward (baselines/caum_plm_module.py:156-163): clicked news [B, S, D] and the dense
+        candidates [B, C, D] -> scores [B, C], column i what ``forward(clicked_news_vector, cand_news_vector[:, i, :])`` returns.
+        Without dropout and with nothing to differentiate (eval() under no_grad / inference_mode, or frozen weights and inputs) it is
+        one library call that takes every history-only and candidate-only product once (``hip.caum_scores_all``).  In train() with
+        p > 0 the reference draws fresh masks of the clicked news per column, and a recorded graph needs the per-column backward:
+        then it is that loop itself over ``forward`` — the same seed draws, bits and gradients as the loop written by hand."""
+        p = self.dropout1.p if self.training else 0.0
+        if p > 0.0 or _differentiable(self, clicked_news_vector, cand_news_vector):
+            scores = torch.zeros(cand_news_vector.shape[0], cand_news_vector.shape[1], device=cand_news_vector.device)
+            scores = scores.transpose(1, 0)
+            for i in range(cand_news_vector.shape[1]):
+                scores[i, :] = self.forward(clicked_news_vector, cand_news_vector[:, i, :])
+            return scores.transpose(1, 0)
+        mha = self.multihead_attention
+        if mha.dropout != 0.0:
+            raise RuntimeError("attention-probability dropout inside nn.MultiheadAttention is not built (the reference uses 0)")
+        if len({self.dropout1.p, self.dropout2.p, self.dropout3.p}) != 1:
+            raise RuntimeError("CAUMUserEncoder: the three dropouts share one probability in the reference; differing ones are not built")
+        return hip.caum_scores_all(clicked_news_vector, cand_news_vector, [t.detach() for t in self._params()], mha.num_heads)
 
 
 class MINSUserEncoder(nn.Module):

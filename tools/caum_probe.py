@@ -1,10 +1,11 @@
 """Time per call of the CAUM baseline's user encoder (csrc/caum.hip through the ``CAUMUserEncoder`` mirror) beside the same restatement
 run as plain float32 torch on the same device, forward and forward + backward, at the shipped widths (S = 50, D = U = F = H1 = 400,
-H2 = 256, 16 heads: head dim 25) for B = 8 and 64 users; the candidate loop of ``CAUMPLMModule.forward`` at C = 5 and C = 40; and the
-share of a call that does not depend on the candidate (the history-side products of the three windows, of linear2 and of nothing
+H2 = 256, 16 heads: head dim 25) for B = 8 and 64 users; the candidate loop of ``CAUMPLMModule.forward`` at C = 5 and C = 40 three
+ways — the loop over the per-column mirror, ``forward_all`` (one library call on shared history products) and the loop over the
+float32 torch composition — with the achieved TFLOP/s of the row-tiled linear inside ``forward_all``; and the share of a call that does not depend on the candidate (the history-side products of the three windows, of linear2 and of nothing
 else: everything past them mixes the candidate in), which is what an eval()-time memo across the loop could save.
 
-Method: every variant is warmed up, then timed in alternating rounds (HIP, torch, HIP, torch, ...) of ``--calls`` calls each with
+Method: every variant is warmed up, then timed in alternating rounds (HIP, torch, HIP, torch, ... — three variants alternate the same way) of ``--calls`` calls each with
 one device synchronise around the round; the figure is the median round over the calls.  These shapes are launch-bound: the figures
 are host-enqueue plus kernel time of a few dozen small launches, not a share of any peak.
 
@@ -13,6 +14,7 @@ are host-enqueue plus kernel time of a few dozen small launches, not a share of 
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 import time
@@ -47,6 +49,47 @@ def rounds(ours, theirs, n_rounds, calls):
         t.append(timed(theirs, calls))
     return {"hip_us": round(statistics.median(a), 2), "torch_f32_us": round(statistics.median(t), 2),
             "hip_min_max_us": [round(min(a), 2), round(max(a), 2)], "torch_min_max_us": [round(min(t), 2), round(max(t), 2)]}
+
+
+def rounds3(variants, n_rounds, calls):
+    """``rounds`` for any number of named variants, alternating within each round: {name_us, name_min_max_us}"""
+    for f in variants.values():
+        timed(f, 3)
+    got = {k: [] for k in variants}
+    for _ in range(n_rounds):
+        for k, f in variants.items():
+            got[k].append(timed(f, calls))
+    out = {}
+    for k, v in got.items():
+        out[k + "_us"] = round(statistics.median(v), 2)
+        out[k + "_min_max_us"] = [round(min(v), 2), round(max(v), 2)]
+    return out
+
+
+def linear_rate(fn, flops):
+    """device time of the launches of the row-tiled linear (wlin_kernel) inside one call of ``fn``, by torch's profiler, and the
+    TFLOP/s that is over the multiply-adds of those launches (the 157.3 TFLOP/s f32 matrix peak is the yardstick)"""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    def device_us(e):
+        return getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0)
+
+    def short(key):                                              # void manner::(anonymous namespace)::wlin_kernel<true, false>(...) -> wlin_kernel<true, false>
+        hit = re.search(r"(\w+_kernel(?:<[^>]*>)?)", key)
+        return hit.group(1) if hit else key[:60]
+    rows = [e for e in prof.key_averages() if "wlin_kernel" in e.key]
+    us, every = sum(device_us(e) for e in rows), sum(device_us(e) for e in prof.key_averages())
+    by_kernel = {}
+    for e in prof.key_averages():
+        if device_us(e) > 0:
+            by_kernel[short(e.key)] = round(by_kernel.get(short(e.key), 0.0) + device_us(e), 2)
+    return {"wlin_launches": sum(e.count for e in rows), "wlin_device_us": round(us, 2), "all_kernels_device_us": round(every, 2),
+            "device_us_by_kernel": dict(sorted(by_kernel.items(), key=lambda kv: -kv[1])),
+            "wlin_gflop": round(flops / 1e9, 3), "wlin_tflops": round(flops / us / 1e6, 2) if us else None, "f32_matrix_peak_tflops": 157.3}
 
 
 def history_side(x, w):
@@ -126,9 +169,21 @@ def main():
                         for i in range(c_n):
                             scores[i, :] = call(cand[:, i, :])
                 return run
+            def all_columns():
+                with torch.no_grad():
+                    enc.forward_all(x, cand)
             calls = max(args.calls // c_n, 5)
-            result["cases"][f"B{b}/module_loop_C{c_n}"] = rounds(loop(lambda cc: enc(x, cc)), loop(lambda cc: ref(x, cc, w)), args.rounds, calls)
-            print(f"B={b} loop C={c_n}: {result['cases'][f'B{b}/module_loop_C{c_n}']}", flush=True)
+            rec = rounds3({"hip": loop(lambda cc: enc(x, cc)), "forward_all": all_columns, "torch_f32": loop(lambda cc: ref(x, cc, w))}, args.rounds, calls)
+            with torch.no_grad():
+                by_loop = torch.stack([enc(x, cand[:, i, :]) for i in range(c_n)], dim=1)
+                rec["max_abs_difference_forward_all_to_the_loop"] = float((enc.forward_all(x, cand) - by_loop).abs().max())
+            r, n, wide = b * S, b * c_n, b * c_n * S                    # rows of the history side, of the candidate side, wide rows
+            flops = 2.0 * (r * (3 * D * F + D * D + 3 * D * D + F * D) + n * (D * F + D * D + 3 * D * D + F * D + D * H1) + D * D * D + D * D
+                           + wide * (D * D + D * H1 + H1 * H2))
+            rec["linear"] = linear_rate(all_columns, flops)
+            rec["wide_rows_gflop"] = round(2.0 * wide * (D * D + D * H1 + H1 * H2) / 1e9, 3)
+            result["cases"][f"B{b}/module_loop_C{c_n}"] = rec
+            print(f"B={b} loop C={c_n}: {rec}", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
