@@ -702,6 +702,35 @@ size_t manner_hip_caum_scores_all_workspace_bytes(int64_t B, int64_t S, int64_t 
 int manner_hip_caum_scores_all(const float* x, const float* cand, const float* const* params, int64_t B, int64_t S, int64_t C, int32_t D, int32_t F,
                                int32_t U, int32_t H1, int32_t H2, int32_t heads, float* out, void* workspace, size_t workspace_bytes,
                                manner_hip_stream_t stream);
+/* manner_hip_caum_train_all_forward / _backward are the candidate loop in one call WITH dropout and gradients (train()): x [B, S, D],
+ * cand contiguous [B, C, D], the same 16 params, seeds a device array of C uint64 (may be NULL when p == 0) -> scores [B, C], column c
+ * what manner_hip_caum_user_forward(x, cand[:, c, :], ..., p, seeds[c], site0) computes: the same three sites and element indices
+ * (dropout1 b D + d, dropout2 (b S + s) D + d, dropout3 (b S + s)(F + U) + j), so the masks of column c are those of the per-column
+ * call with that seed.  The reference draws a fresh mask of the clicked news per column, so nothing is shared between the columns:
+ * the B C S rows run in (b, c, s) order through one launch per product — the f32 matrix-core linear forward and for the data
+ * gradients, manner_hip_wgrad_rows_f32's kernel for the weight gradients (from 64 rows on; the per-column entry's below).  `saved` (_saved_bytes) keeps the activations for _backward,
+ * which fills grad_x [B, S, D] (the columns' contributions added in ascending c, each through its own dropout2 mask),
+ * grad_cand [B, C, D] and the 16 parameter gradients (the same two written as exact zeros); `workspace` as
+ * _backward_workspace_bytes says.  Limits and messages as manner_hip_caum_user_forward under the prefixes caum_train_all /
+ * caum_train_all_backward, and B C S < 2^31.  Forward: C == 0 or B == 0 writes nothing.  Backward: C == 0 or B == 0 zero-fills the
+ * parameter gradients, and grad_x as well when C == 0.  C < 0 is MANNER_HIP_E_INVALID.
+ * manner_hip_wgrad_rows_f32: dW[o, k] = sum_r dy[r, o] x[r, k] in true f32 on the matrix cores (dy rows ldy, x rows ldx, dW rows ldo
+ * floats apart).  The rows are split into groups whose count depends on (R, K, O) alone; the partial sums live in `workspace`
+ * (_workspace_bytes; 0 when one group takes all rows) and are added in ascending group order: no atomics, the same bits every run.
+ * R == 0 writes zeros. */
+size_t manner_hip_caum_train_all_saved_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads);
+int manner_hip_caum_train_all_forward(const float* x, const float* cand, const float* const* params, int64_t B, int64_t S, int64_t C, int32_t D,
+                                      int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads, float p, const uint64_t* seeds, uint32_t site0,
+                                      float* scores, void* saved, size_t saved_bytes, manner_hip_stream_t stream);
+size_t manner_hip_caum_train_all_backward_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2,
+                                                          int32_t heads);
+int manner_hip_caum_train_all_backward(const float* const* params, const float* grad_scores, int64_t B, int64_t S, int64_t C, int32_t D, int32_t F,
+                                       int32_t U, int32_t H1, int32_t H2, int32_t heads, float p, const uint64_t* seeds, uint32_t site0, void* saved,
+                                       size_t saved_bytes, float* grad_x, float* grad_cand, float* const* grads, void* workspace,
+                                       size_t workspace_bytes, manner_hip_stream_t stream);
+size_t manner_hip_wgrad_rows_f32_workspace_bytes(int64_t R, int32_t K, int32_t O);
+int manner_hip_wgrad_rows_f32(const float* dy, int32_t ldy, const float* x, int32_t ldx, int64_t R, int32_t K, int32_t O, float* dW, int32_t ldo,
+                              void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
 /* DenseAttention alone (attention.py:134-141): y [R, O] = tanh(x W^T + b), and grad_pre = grad_out (1 - y^2) for its backward */
 int manner_hip_linear_tanh(const float* x, const float* weight, const float* bias, int64_t R, int32_t K, int32_t O, float* y,
                            manner_hip_stream_t stream);

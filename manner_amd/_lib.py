@@ -140,6 +140,14 @@ SIGNATURES = {
                                                 C.c_uint32, _P, _SZ, _P, _P, C.POINTER(_P), _P, _SZ, _P]),
     "manner_hip_caum_scores_all_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I64]),
     "manner_hip_caum_scores_all": (C.c_int, [_P, _P, C.POINTER(_P), _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _SZ, _P]),
+    "manner_hip_caum_train_all_saved_bytes": (_SZ, [_I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "manner_hip_caum_train_all_forward": (C.c_int, [_P, _P, C.POINTER(_P), _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, C.c_float, _P,
+                                                    C.c_uint32, _P, _P, _SZ, _P]),
+    "manner_hip_caum_train_all_backward_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "manner_hip_caum_train_all_backward": (C.c_int, [C.POINTER(_P), _P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, C.c_float, _P,
+                                                     C.c_uint32, _P, _SZ, _P, _P, C.POINTER(_P), _P, _SZ, _P]),
+    "manner_hip_wgrad_rows_f32_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "manner_hip_wgrad_rows_f32": (C.c_int, [_P, _I32, _P, _I32, _I64, _I32, _I32, _P, _I32, _P, _SZ, _P]),
     "manner_hip_linear_tanh": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P]),
     "manner_hip_tanh_backward": (C.c_int, [_P, _P, _P, _I64, _P]),
     "manner_hip_relu": (C.c_int, [_P, _P, _I64, _P]),

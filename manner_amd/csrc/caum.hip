@@ -8,7 +8,9 @@
 // Linear is computed once per user.  nn.MultiheadAttention is batch_first=False but fed [B, S, U]: attention runs ACROSS THE B USERS
 // of the call at each history slot (as in the reference's other batch_first=False calls), so B is the key axis.
 // manner_hip_caum_scores_all (the last section) scores ALL candidate columns of a dense [B, C, D] tensor in one call, eval() only, on
-// shared history products and an f32 MFMA linear.
+// shared history products and an f32 MFMA linear.  manner_hip_caum_train_all_forward / _backward (after it) are the same loop in train():
+// all columns as B C S rows of one call, column c under its own dropout seed, forward and backward, every product on the matrix cores
+// (wlin_kernel; mwgrad_kernel for the weight gradients, exported alone as manner_hip_wgrad_rows_f32).
 // The per-column workload is small (B = 8, S = 50, widths 400) and latency-bound: plain f32 VALU kernels.  Every reduction across rows runs in a
 // fixed order (no floating-point atomics): two runs give the same bits.
 #include <math.h>
@@ -682,7 +684,8 @@ void plan_saved(Bump& b, Saved& s, const Dims& m) {
   s.g = b.take(R);
 }
 struct Work { float *ds, *wq, *dt2, *dt1, *dall, *dct, *dcd, *dcat, *datt, *dqkv, *dh2, *da2, *da1, *part; };
-void plan_work(Bump& b, Work& w, const Dims& m) {
+// everything but the partial sums of the weight gradients
+void plan_work_rows(Bump& b, Work& w, const Dims& m) {
   const size_t R = (size_t)m.R, B = (size_t)m.B;
   w.ds = b.take(R);
   w.wq = b.take(R);
@@ -697,6 +700,9 @@ void plan_work(Bump& b, Work& w, const Dims& m) {
   w.dh2 = b.take(R * m.U);
   w.da2 = b.take(R * 2 * m.D);
   w.da1 = b.take(R * 4 * m.D);
+}
+void plan_work(Bump& b, Work& w, const Dims& m) {
+  plan_work_rows(b, w, m);
   const size_t ok = std::max({(size_t)m.F * 4 * m.D, (size_t)m.U * 2 * m.D, (size_t)3 * m.U * m.U, (size_t)m.U * (m.F + m.U), (size_t)m.H1 * m.U,
                               (size_t)m.H2 * m.H1, (size_t)m.H2});
   w.part = b.take((size_t)wgrad_groups(m.R) * ok);
@@ -722,13 +728,16 @@ struct RowMap { int S, cp, C, c0; };
 //   128 rows x 64 output features, grid (ceil(R / 128), ceil(O / 64)): each wave takes 32 rows x 64 features on v_mfma_f32_32x32x2_f32;
 //   SMALL, 32 x 32, grid (ceil(R / 32), ceil(O / 32)): each wave takes a 16 x 16 quarter on v_mfma_f32_16x16x4_f32 — for the launches of a
 //     few hundred rows (the history side and the candidate side at B = 8), which the large tile leaves on a few dozen workgroups.
+// `deriv` [R, O] (TANH only, may be NULL): tanh' = 4 e / (1 + e)^2 from the pre-activation; add_el / mul_el [R, O] (may be NULL): the
+// elementwise terms of a data gradient, y = (add_el + sum) * mul_el.
 // Either way a workgroup stages its rows and weight rows per 32 input features (the next step's floats wait in registers while this
 // one multiplies), and an output is one k-ascending fmaf chain whatever its place in a tile and whichever tile: a row's bits do not
 // depend on the tile, the pass or the row count of the launch.
 template <bool TANH, bool SMALL>
 __global__ __launch_bounds__(CA_BLOCK) void wlin_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ W, int ldw,
                                                    const float* __restrict__ bias, const float* __restrict__ add_bs,
-                                                   const float* __restrict__ add_bc, RowMap m, int64_t R, int K, int O, float* __restrict__ y, int ldy) {
+                                                   const float* __restrict__ add_bc, RowMap m, int64_t R, int K, int O, float* __restrict__ y, int ldy,
+                                                   float* __restrict__ deriv, const float* __restrict__ add_el, const float* __restrict__ mul_el) {
   constexpr int BM = SMALL ? 32 : 128, BN = SMALL ? 32 : 64;
   constexpr int SROWS = CA_BLOCK / WL_BK, XV = BM / SROWS, WV = BN / SROWS;        // staging: 8 rows per sweep; floats per thread of x, of W
   __shared__ float xs[BM][WL_LD];
@@ -764,7 +773,13 @@ __global__ __launch_bounds__(CA_BLOCK) void wlin_kernel(const float* __restrict_
       if (add_bs) v += add_bs[((size_t)b * m.S + s) * O + o];
       if (add_bc) v += add_bc[((size_t)b * m.C + m.c0 + cl) * O + o];
     }
+    if (add_el) v += add_el[(size_t)r * O + o];          // the data gradients: (add + sum) * mul, as lin_dx_kernel
+    if (mul_el) v *= mul_el[(size_t)r * O + o];
     y[(size_t)r * ldy + o] = TANH ? tanhf(v) : v;
+    if (TANH && deriv) {                                 // tanh' from the pre-activation, as lin_kernel
+      const float e = expf(-2.0f * fabsf(v)), den = 1.0f + e;
+      deriv[(size_t)r * O + o] = 4.0f * e / (den * den);
+    }
   };
   f32x16 acc0, acc1;
   f32x4 accs;
@@ -808,11 +823,12 @@ __global__ __launch_bounds__(CA_BLOCK) void wlin_kernel(const float* __restrict_
   }
 }
 int launch_wlin(bool tanh_act, const float* x, int ldx, const float* W, int ldw, const float* bias, const float* add_bs, const float* add_bc, RowMap m,
-                int64_t R, int K, int O, float* y, int ldy, hipStream_t s) {
+                int64_t R, int K, int O, float* y, int ldy, hipStream_t s, float* deriv = nullptr, const float* add_el = nullptr,
+                const float* mul_el = nullptr) {
   const bool small = R < WL_SMALL_ROWS;
   const int bm = small ? 32 : 128, bn = small ? 32 : 64;
   const dim3 g((unsigned)((R + bm - 1) / bm), (unsigned)((O + bn - 1) / bn));
-#define MANNER_WLIN(T_, S_) hipLaunchKernelGGL((wlin_kernel<T_, S_>), g, dim3(CA_BLOCK), 0, s, x, ldx, W, ldw, bias, add_bs, add_bc, m, R, K, O, y, ldy)
+#define MANNER_WLIN(T_, S_) hipLaunchKernelGGL((wlin_kernel<T_, S_>), g, dim3(CA_BLOCK), 0, s, x, ldx, W, ldw, bias, add_bs, add_bc, m, R, K, O, y, ldy, deriv, add_el, mul_el)
   if (tanh_act && small) MANNER_WLIN(true, true);
   else if (tanh_act) MANNER_WLIN(true, false);
   else if (small) MANNER_WLIN(false, true);
@@ -967,6 +983,253 @@ int caum_all_check(const char* who, int64_t B, int64_t S, int64_t C, int D, int 
   if (B * std::max<int64_t>(C, 1) > 0x7fffffffll || std::max<int64_t>(B, heads) * S > 0x7fffffffll)
     return fail(MANNER_HIP_E_INVALID, "%s: B*C or one column's rows exceed the grid", who);
   return MANNER_HIP_OK;
+}
+
+// ---------------------------------------------------------------- training over all candidate columns
+// The per-column training entry with the C columns as rows: R' = B C S rows in (b, c, s) order, (b, c) a pseudo-user of S slots, so
+// that score_kernel, user_kernel, tail_rows_kernel, segsum_kernel and colsum_kernel run as they are and the attention sees
+// qkv [B, C S, 3U].  Nothing is shared between the columns — the reference draws a fresh dropout2 mask of the clicked news per column —
+// but every product runs once over C times the rows, on the matrix cores: wlin_kernel forward and for the data gradients (over a weight
+// transposed once per call), mwgrad_kernel for the weight gradients.  Column c draws with seeds[c] at the element indices of the
+// per-column call, so its masks are those of manner_hip_caum_user_forward with that seed.
+__device__ __forceinline__ Drop col_drop(Drop d, const uint64_t* __restrict__ seeds, int c) {
+  if (seeds) d.seed = seeds[c];
+  return d;
+}
+// grid (B C S): pack_kernel for row (b, c, s) — x[b, s +- 1] circular inside the S slots, cand[b, c], the column's seed
+__global__ __launch_bounds__(CA_BLOCK) void pack_cols_kernel(const float* __restrict__ x, const float* __restrict__ cand, int S, int C, int D, Drop d1,
+                                                        Drop d2, const uint64_t* __restrict__ seeds, float* __restrict__ a1, float* __restrict__ a2,
+                                                        float* __restrict__ cd) {
+  const int64_t r = blockIdx.x, pu = r / S, b = pu / C;
+  const int s = (int)(r - pu * S), c = (int)(pu - b * C);
+  const int sl = s == 0 ? S - 1 : s - 1, sr = s == S - 1 ? 0 : s + 1;
+  d1 = col_drop(d1, seeds, c);
+  d2 = col_drop(d2, seeds, c);
+  const size_t xb = (size_t)b * S * D;
+  for (int d = threadIdx.x; d < D; d += CA_BLOCK) {
+    const size_t il = xb + (size_t)sl * D + d, im = xb + (size_t)s * D + d, ir = xb + (size_t)sr * D + d;
+    const float vl = d2.apply(x[il], il), vm = d2.apply(x[im], im), vr = d2.apply(x[ir], ir);
+    const float cv = d1.apply(cand[(size_t)pu * D + d], (uint64_t)b * D + d);
+    float* p1 = a1 + (size_t)r * 4 * D;
+    p1[d] = vl; p1[D + d] = vm; p1[2 * D + d] = vr; p1[3 * D + d] = cv;
+    float* p2 = a2 + (size_t)r * 2 * D;
+    p2[d] = cv; p2[D + d] = vm;
+    if (s == 0) cd[(size_t)pu * D + d] = cv;
+  }
+}
+// dropout3 (and its backward) on [B C S, W] rows: element j of row (b, c, s) draws at (b S + s) W + j with the column's seed
+__global__ __launch_bounds__(CA_BLOCK) void drop_cols_kernel(float* x, int64_t n, int S, int C, int W, Drop d3, const uint64_t* __restrict__ seeds) {
+  for (int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * CA_BLOCK) {
+    const int64_t r = i / W, pu = r / S, b = pu / C;
+    const int j = (int)(i - r * W), s = (int)(r - pu * S), c = (int)(pu - b * C);
+    x[i] = col_drop(d3, seeds, c).apply(x[i], (uint64_t)(b * S + s) * W + j);
+  }
+}
+// grid (B S): window_dx_kernel's gather for each column, masked by the column's dropout2, the C columns added in ascending c on one chain
+__global__ __launch_bounds__(CA_BLOCK) void window_dx_cols_kernel(const float* __restrict__ da1, const float* __restrict__ da2, int S, int C, int D, Drop d2,
+                                                             const uint64_t* __restrict__ seeds, float* __restrict__ dx) {
+  const int64_t r = blockIdx.x, b = r / S;
+  const int s = (int)(r - b * S);
+  const int sl = s == 0 ? S - 1 : s - 1, sr = s == S - 1 ? 0 : s + 1;
+  for (int d = threadIdx.x; d < D; d += CA_BLOCK) {
+    const size_t at = (size_t)r * D + d;
+    float acc = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const size_t rb = ((size_t)b * C + c) * S;
+      const float v = ((da1[(rb + sr) * 4 * D + d] + da1[(rb + s) * 4 * D + D + d]) + da1[(rb + sl) * 4 * D + 2 * D + d]) + da2[(rb + s) * 2 * D + D + d];
+      const float m = col_drop(d2, seeds, c).apply(v, at);
+      acc = c == 0 ? m : acc + m;
+    }
+    dx[at] = acc;
+  }
+}
+// grid (B C, ceil(D / 256)): d cand[b, c] = dropout1-mask(dcd[b, c] + sum_s (da1[b, c, s][3D:] + da2[b, c, s][:D])) — segsum_kernel's sum on two
+// chains, the mask by the column's seed at b D + d
+__global__ __launch_bounds__(CA_BLOCK) void cand_dx_cols_kernel(const float* __restrict__ da1, const float* __restrict__ da2, const float* __restrict__ dcd, int S,
+                                                           int C, int D, Drop d1, const uint64_t* __restrict__ seeds, float* __restrict__ out) {
+  const int64_t pu = blockIdx.x, b = pu / C;
+  const int c = (int)(pu - b * C), j = blockIdx.y * CA_BLOCK + threadIdx.x;
+  if (j >= D) return;
+  float a0 = 0.f, a1 = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const size_t r = (size_t)pu * S + s;
+    const float v = da1[r * 4 * D + 3 * D + j] + da2[r * 2 * D + j];
+    if (s & 1) a1 += v; else a0 += v;
+  }
+  out[(size_t)pu * D + j] = col_drop(d1, seeds, c).apply((a0 + a1) + dcd[(size_t)pu * D + j], (uint64_t)b * D + j);
+}
+// out[k, o] = in[o, k]: in [O, K] rows ldw apart (a column range of a weight), out [K, O] contiguous — the operand of a data gradient
+// dx = dy W as wlin_kernel's row-times-row product.  grid (ceil(K / 32), ceil(O / 32)), a 32 x 32 tile through LDS, both sides coalesced.
+__global__ __launch_bounds__(CA_BLOCK) void transpose_ld_kernel(const float* __restrict__ in, int ldw, int O, int K, float* __restrict__ out) {
+  __shared__ float t[32][33];
+  const int k0 = blockIdx.x * 32, o0 = blockIdx.y * 32, tx = threadIdx.x % 32, ty = threadIdx.x / 32;
+  for (int i = ty; i < 32; i += CA_BLOCK / 32)
+    t[i][tx] = (o0 + i < O && k0 + tx < K) ? in[(size_t)(o0 + i) * ldw + k0 + tx] : 0.f;
+  __syncthreads();
+  for (int i = ty; i < 32; i += CA_BLOCK / 32)
+    if (k0 + i < K && o0 + tx < O) out[(size_t)(k0 + i) * O + o0 + tx] = t[tx][i];
+}
+
+// dW[o, k] = sum_r dy[r, o] x[r, k] on the matrix cores, true f32: the product dy^T x with the ROWS as the contraction axis.  dy rows
+// ldy apart, x rows ldx apart.  grid (ceil(K / BK), ceil(O / BO), G) in two tiles, as wlin_kernel:
+//   64 output x 128 input features: wave = (o half, k half), 32 x 64 as two accumulators of v_mfma_f32_32x32x2_f32;
+//   SMALL (O or K below 64), 32 x 32: each wave a 16 x 16 quarter on v_mfma_f32_16x16x4_f32.
+// Group g walks its rows [g chunk, (g + 1) chunk) in stagings of MW_RB rows: the dy and x rows go to LDS as they lie in memory (row-major,
+// coalesced; the next staging's floats wait in registers while this one multiplies) and are the MFMA operands as they lie there:
+// A[i = o][k = r] = dys[r][o], B[k = r][j = k] = xs[r][k].  Large tile: the 32 lanes of a ds_read_b32 group read consecutive floats of
+// one row, conflict-free at any pitch.  Small tile: a group is 16 columns of two consecutive rows, which a pitch of 32 floats would put
+// on the same 16 banks (2-way); the rows are MW_SMALL_PAD floats longer, so the second row starts 16 banks on.
+// An output is one r-ascending fmaf chain per group (rows past the group's end are zeros); the G partial sums part[g][o][k] are added in ascending g by wgrad_reduce_kernel (G == 1 writes dW itself).  No atomics: the same bits
+// every run.
+constexpr int MW_RB = 32;            // rows per staging
+constexpr int MW_MAX_GROUPS = 64;    // most row groups
+constexpr int MW_FILL = 512;         // workgroups a launch aims at (2 per CU)
+constexpr int MW_SMALL_PAD = 16;     // small tile: LDS rows 48 floats apart, so that the two rows of a 32-lane read group sit 16 banks apart
+template <bool SMALL>
+__global__ __launch_bounds__(CA_BLOCK) void mwgrad_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ x, int ldx, int64_t R, int K, int O,
+                                                     int64_t chunk, float* __restrict__ out, int ldo, int64_t gstride) {
+  constexpr int BO = SMALL ? 32 : 64, BK = SMALL ? 32 : 128;
+  constexpr int DV = MW_RB * BO / CA_BLOCK, XV = MW_RB * BK / CA_BLOCK;      // floats per thread of a staging
+  constexpr int DROWS = CA_BLOCK / BO, XROWS = CA_BLOCK / BK;                  // rows per sweep of the staging threads
+  constexpr int PAD = SMALL ? MW_SMALL_PAD : 0;
+  __shared__ float dys[MW_RB][BO + PAD];
+  __shared__ float xs[MW_RB][BK + PAD];
+  const int tid = threadIdx.x, wave = tid / CA_WAVE, lane = tid % CA_WAVE;
+  const int k0 = blockIdx.x * BK, o0 = blockIdx.y * BO;
+  const int64_t r0 = (int64_t)blockIdx.z * chunk, r1 = min(R, r0 + chunk);
+  const int dc = tid % BO, dr = tid / BO, xc = tid % BK, xr = tid / BK;
+  float dv[DV], xv[XV];
+  auto fetch = [&](int64_t rb) {
+#pragma unroll
+    for (int i = 0; i < DV; ++i) {
+      const int64_t r = rb + dr + i * DROWS;
+      dv[i] = (r < r1 && o0 + dc < O) ? dy[(size_t)r * ldy + o0 + dc] : 0.f;           // past the group, O or K: zeros, no branch below
+    }
+#pragma unroll
+    for (int i = 0; i < XV; ++i) {
+      const int64_t r = rb + xr + i * XROWS;
+      xv[i] = (r < r1 && k0 + xc < K) ? x[(size_t)r * ldx + k0 + xc] : 0.f;
+    }
+  };
+  f32x16 acc0, acc1;
+  f32x4 accs;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) accs[i] = 0.f;
+  fetch(r0);
+  for (int64_t rb = r0; rb < r1; rb += MW_RB) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < DV; ++i) dys[dr + i * DROWS][dc] = dv[i];
+#pragma unroll
+    for (int i = 0; i < XV; ++i) xs[xr + i * XROWS][xc] = xv[i];
+    __syncthreads();
+    if (rb + MW_RB < r1) fetch(rb + MW_RB);
+    if constexpr (SMALL) {                               // operand maps: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15]
+      const int ao = (wave >> 1) * 16 + (lane & 15), bk = (wave & 1) * 16 + (lane & 15), rq = lane >> 4;
+#pragma unroll
+      for (int rr = 0; rr < MW_RB; rr += 4) accs = __builtin_amdgcn_mfma_f32_16x16x4f32(dys[rr + rq][ao], xs[rr + rq][bk], accs, 0, 0, 0);
+    } else {                                             // A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
+      const int ao = (wave & 1) * 32 + (lane & 31), bk = (wave >> 1) * 64 + (lane & 31), rh = lane >> 5;
+#pragma unroll
+      for (int rr = 0; rr < MW_RB; rr += 2) {
+        const float a = dys[rr + rh][ao];
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, xs[rr + rh][bk], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, xs[rr + rh][bk + 32], acc1, 0, 0, 0);
+      }
+    }
+  }
+  float* dst = out + (size_t)blockIdx.z * gstride;
+  auto emit = [&](int oo, int kk, float v) {
+    if (o0 + oo < O && k0 + kk < K) dst[(size_t)(o0 + oo) * ldo + k0 + kk] = v;
+  };
+  if constexpr (SMALL) {                                 // C / D map: column = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) emit((wave >> 1) * 16 + 4 * (lane >> 4) + reg, (wave & 1) * 16 + (lane & 15), accs[reg]);
+  } else {                                               // C / D map: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int oo = (wave & 1) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+      emit(oo, (wave >> 1) * 64 + (lane & 31), acc0[reg]);
+      emit(oo, (wave >> 1) * 64 + 32 + (lane & 31), acc1[reg]);
+    }
+  }
+}
+// the split of a launch: a function of (R, O, K) alone.  Enough row groups for MW_FILL workgroups — the H2 x H1 and 1 x H2 products have a
+// handful of (o, k) tiles — of at least one staging each, in whole stagings.
+struct MwPlan { bool small; int G; int64_t chunk; };
+MwPlan mw_plan(int64_t R, int K, int O) {
+  MwPlan p;
+  p.small = O < 64 || K < 64;
+  const int64_t tiles = p.small ? (int64_t)((O + 31) / 32) * ((K + 31) / 32) : (int64_t)((O + 63) / 64) * ((K + 127) / 128);
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>({(int64_t)MW_MAX_GROUPS, (MW_FILL + tiles - 1) / tiles, R / MW_RB}));
+  p.chunk = ((R + want - 1) / want + MW_RB - 1) / MW_RB * MW_RB;
+  p.G = (int)((R + p.chunk - 1) / p.chunk);
+  return p;
+}
+size_t mw_part_floats(int64_t R, int K, int O) {
+  const MwPlan p = mw_plan(R, K, O);
+  return p.G > 1 ? (size_t)p.G * O * K : 0;
+}
+// R >= 1; part holds mw_part_floats(R, K, O) floats
+int launch_mwgrad(const float* dy, int ldy, const float* x, int ldx, int64_t R, int K, int O, float* part, float* dW, int ldo, hipStream_t s) {
+  const MwPlan p = mw_plan(R, K, O);
+  const int bo = p.small ? 32 : 64, bk = p.small ? 32 : 128;
+  const dim3 g((unsigned)((K + bk - 1) / bk), (unsigned)((O + bo - 1) / bo), (unsigned)p.G);
+  float* out = p.G == 1 ? dW : part;
+  const int ld = p.G == 1 ? ldo : K;
+  const int64_t gs = p.G == 1 ? 0 : (int64_t)O * K;
+  if (p.small) hipLaunchKernelGGL(mwgrad_kernel<true>, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, ldx, R, K, O, p.chunk, out, ld, gs);
+  else hipLaunchKernelGGL(mwgrad_kernel<false>, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, ldx, R, K, O, p.chunk, out, ld, gs);
+  MANNER_LAUNCH_CHECK();
+  if (p.G > 1) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((int64_t)O * K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, part, K, O, p.G, dW, ldo);
+    MANNER_LAUNCH_CHECK();
+  }
+  return MANNER_HIP_OK;
+}
+// the weight gradients of the all-columns backward, selected per launch by the row count alone: at equal (R, K, O) of the shipped widths
+// (profiles/caum/kernel_trace.json, weight_gradient_equal_shapes) mwgrad_kernel is 2.1 - 7.7 x wgrad_rows_kernel from 320 rows on and
+// slower only at the 40 rows of the B C pairs at B = 8 (7.3 against 5.6 us: one staging, 28 workgroups) — below MW_MIN_ROWS rows the
+// one-thread-per-(o, k) kernel runs, in one group (wgrad_groups: no partial sums).  x [R, K] contiguous.
+constexpr int MW_MIN_ROWS = 64;
+static_assert(MW_MIN_ROWS <= WG_ROWS, "below MW_MIN_ROWS rows wgrad_rows_kernel writes dW itself");
+int launch_wgrad_all(const float* dy, int ldy, const float* x, int64_t R, int K, int O, float* part, float* dW, int ldo, hipStream_t s) {
+  if (R < MW_MIN_ROWS) return launch_wgrad(dy, ldy, x, R, K, O, nullptr, dW, ldo, s);
+  return launch_mwgrad(dy, ldy, x, K, R, K, O, part, dW, ldo, s);
+}
+// dx [R, K] = (add + dy W) * mul on wlin_kernel: W [O, K] (rows ldw apart) transposed into wt [K, O] first
+int launch_mdx(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, const float* add, const float* mul, float* dx, float* wt,
+               hipStream_t s) {
+  hipLaunchKernelGGL(transpose_ld_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)((O + 31) / 32)), dim3(CA_BLOCK), 0, s, W, ldw, O, K, wt);
+  MANNER_LAUNCH_CHECK();
+  return launch_wlin(false, dy, ldy, wt, O, nullptr, nullptr, nullptr, RowMap{1, 1, 1, 0}, R, O, K, dx, K, s, nullptr, add, mul);
+}
+
+// the wide view of a call: P = B C pseudo-users, R = B C S rows
+int caum_train_all_check(const char* who, int64_t B, int64_t S, int64_t C, int D, int F, int U, int H1, int H2, int heads, Dims& m) {
+  int rc;
+  if ((rc = caum_check(who, B, S, D, F, U, H1, H2, heads, m))) return rc;
+  if (C < 0) return fail(MANNER_HIP_E_INVALID, "%s: bad shape C=%lld", who, (long long)C);
+  if (B * std::max<int64_t>(C, 1) > 0x7fffffffll || B * std::max<int64_t>(C, 1) * S > 0x7fffffffll || C * S * heads > 0x7fffffffll)
+    return fail(MANNER_HIP_E_INVALID, "%s: B*C*S or C*S*heads exceeds the grid (below 2^31)", who);
+  m = Dims{B * C, S, B * C * S, D, F, U, H1, H2, heads};
+  return MANNER_HIP_OK;
+}
+struct WorkAll { Work w; float *dall2, *dcd2, *wt, *mpart; };
+void plan_work_all(Bump& b, WorkAll& a, const Dims& m) {
+  const size_t R = (size_t)m.R, P = (size_t)m.B;
+  plan_work_rows(b, a.w, m);
+  a.w.part = nullptr;
+  a.dall2 = b.take(R * m.U);
+  a.dcd2 = b.take(P * m.D);
+  a.wt = b.take(std::max({(size_t)m.F * 4 * m.D, (size_t)m.U * 2 * m.D, (size_t)3 * m.U * m.U, (size_t)m.U * (m.F + m.U), (size_t)m.H1 * m.U,
+                          (size_t)m.H1 * m.D, (size_t)m.H2 * m.H1}));
+  const int FU = m.F + m.U;
+  a.mpart = b.take(std::max({mw_part_floats(m.R, m.H2, 1), mw_part_floats(m.R, m.H1, m.H2), mw_part_floats(m.R, m.U, m.H1),
+                             mw_part_floats(m.B, m.D, m.H1), mw_part_floats(m.R, FU, m.U), mw_part_floats(m.R, m.U, m.U),
+                             mw_part_floats(m.R, m.U, 3 * m.U), mw_part_floats(m.R, 2 * m.D, m.U), mw_part_floats(m.R, 4 * m.D, m.F)}));
 }
 
 }  // namespace
@@ -1270,6 +1533,195 @@ int manner_hip_caum_scores_all(const float* x, const float* cand, const float* c
       MANNER_LAUNCH_CHECK();
     }
   }
+  return MANNER_HIP_OK;
+}
+
+size_t manner_hip_wgrad_rows_f32_workspace_bytes(int64_t R, int32_t K, int32_t O) {
+  if (R <= 0 || K <= 0 || O <= 0) return 0;
+  return mw_part_floats(R, K, O) * sizeof(float);
+}
+
+int manner_hip_wgrad_rows_f32(const float* dy, int32_t ldy, const float* x, int32_t ldx, int64_t R, int32_t K, int32_t O, float* dW, int32_t ldo,
+                              void* workspace, size_t workspace_bytes, manner_hip_stream_t stream) {
+  if (R < 0 || K <= 0 || O <= 0 || ldy < O || ldx < K || ldo < K || R > 0x7fffffffll || O > 65535 * 32)
+    return fail(MANNER_HIP_E_INVALID, "wgrad_rows_f32: bad shape R=%lld K=%d O=%d ldy=%d ldx=%d ldo=%d", (long long)R, K, O, ldy, ldx, ldo);
+  if (!dW) return fail(MANNER_HIP_E_INVALID, "wgrad_rows_f32: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (R == 0) {                                    // a sum over nothing
+    MANNER_HIP_TRY(hipMemset2DAsync(dW, (size_t)ldo * sizeof(float), 0, (size_t)K * sizeof(float), (size_t)O, s));
+    return MANNER_HIP_OK;
+  }
+  if (!dy || !x) return fail(MANNER_HIP_E_INVALID, "wgrad_rows_f32: null pointer");
+  const size_t need = mw_part_floats(R, K, O) * sizeof(float);
+  if (need && (!workspace || workspace_bytes < need)) return fail(MANNER_HIP_E_WORKSPACE, "wgrad_rows_f32: workspace too small (%zu bytes)", need);
+  return launch_mwgrad(dy, ldy, x, ldx, R, K, O, static_cast<float*>(workspace), dW, ldo, s);
+}
+
+size_t manner_hip_caum_train_all_saved_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads) {
+  if (B <= 0 || S <= 0 || C <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
+  const Dims m{B * C, S, B * C * S, D, F, U, H1, H2, heads};
+  Bump b(nullptr);
+  Saved s;
+  plan_saved(b, s, m);
+  return b.off * sizeof(float) + 256;
+}
+
+int manner_hip_caum_train_all_forward(const float* x, const float* cand, const float* const* params, int64_t B, int64_t S, int64_t C, int32_t D,
+                                      int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads, float p, const uint64_t* seeds, uint32_t site0,
+                                      float* scores, void* saved, size_t saved_bytes, manner_hip_stream_t stream) {
+  int rc;
+  Dims m;
+  if ((rc = caum_train_all_check("caum_train_all", B, S, C, D, F, U, H1, H2, heads, m))) return rc;
+  if (!(p >= 0.f && p < 1.f)) return fail(MANNER_HIP_E_INVALID, "caum_train_all: p=%f outside [0, 1)", p);
+  if (B == 0 || C == 0) return MANNER_HIP_OK;
+  if (!x || !cand || !params || !scores || !saved || (p > 0.f && !seeds)) return fail(MANNER_HIP_E_INVALID, "caum_train_all: null pointer");
+  for (int i = 0; i < P_COUNT; ++i)
+    if (!params[i]) return fail(MANNER_HIP_E_INVALID, "caum_train_all: null parameter %d", i);
+  if (saved_bytes < manner_hip_caum_train_all_saved_bytes(B, S, C, D, F, U, H1, H2, heads)) return fail(MANNER_HIP_E_WORKSPACE, "caum_train_all: saved buffer too small");
+  hipStream_t s = (hipStream_t)stream;
+  Bump bump(saved);
+  Saved sv;
+  plan_saved(bump, sv, m);
+  const int64_t R = m.R, P = m.B;
+  const int FU = F + U, Si = (int)S, Ci = (int)C;
+  const Drop d1 = make_drop(0, site0, p), d2 = make_drop(0, site0 + 1, p), d3 = make_drop(0, site0 + 2, p);      // the seed is the column's
+  const RowMap flat{1, 1, 1, 0}, wide{Si, Ci, Ci, 0};
+  const float* const none = nullptr;
+  hipLaunchKernelGGL(pack_cols_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, x, cand, Si, Ci, D, d1, d2, seeds, sv.a1, sv.a2, sv.cd);
+  MANNER_LAUNCH_CHECK();
+  // candi-cnn into cat[:, :F]; candi-selfatt: Linear, in-projection, attention along B per (column, slot, head), out-projection into cat[:, F:]
+  if ((rc = launch_wlin(false, sv.a1, 4 * D, params[P_W1], 4 * D, params[P_B1], none, none, flat, R, 4 * D, F, sv.cat, FU, s))) return rc;
+  if ((rc = launch_wlin(false, sv.a2, 2 * D, params[P_W2], 2 * D, params[P_B2], none, none, flat, R, 2 * D, U, sv.h2, U, s))) return rc;
+  if ((rc = launch_wlin(false, sv.h2, U, params[P_WIN], U, params[P_BIN], none, none, flat, R, U, 3 * U, sv.qkv, 3 * U, s))) return rc;
+  if ((rc = launch_a0any_fwd(sv.qkv, sv.att, sv.stats, B, C * S, U, heads, s))) return rc;
+  if ((rc = launch_wlin(false, sv.att, U, params[P_WOUT], U, params[P_BOUT], none, none, flat, R, U, U, sv.cat + F, FU, s))) return rc;
+  if (p > 0.f) {
+    hipLaunchKernelGGL(drop_cols_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, sv.cat, R * FU, Si, Ci, FU, d3, seeds);
+    MANNER_LAUNCH_CHECK();
+  }
+  if ((rc = launch_wlin(false, sv.cat, FU, params[P_W3], FU, params[P_B3], none, none, flat, R, FU, U, sv.all, U, s))) return rc;
+  // candi-att: the candidate half of dense_att.linear once per (user, column), then the two tanh layers over the rows
+  if ((rc = launch_wlin(false, sv.cd, D, params[P_WA] + U, 2 * U, params[P_BA], none, none, flat, P, D, H1, sv.ct, H1, s))) return rc;
+  if ((rc = launch_wlin(true, sv.all, U, params[P_WA], 2 * U, none, none, sv.ct, wide, R, U, H1, sv.t1, H1, s, sv.d1))) return rc;
+  if ((rc = launch_wlin(true, sv.t1, H1, params[P_WB], H1, params[P_BB], none, none, flat, R, H1, H2, sv.t2, H2, s, sv.d2))) return rc;
+  hipLaunchKernelGGL(score_kernel, dim3((unsigned)((R + CA_ROWS - 1) / CA_ROWS)), dim3(CA_BLOCK), 0, s, sv.t2, params[P_WC], params[P_BC], sv.all, sv.cd, R,
+                     Si, H2, U, sv.score, sv.g);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(user_kernel, dim3((unsigned)((P + CA_WAVES - 1) / CA_WAVES)), dim3(CA_BLOCK), 0, s, sv.score, sv.g, P, Si, scores, (const float*)nullptr,
+                     (float*)nullptr, (float*)nullptr);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+size_t manner_hip_caum_train_all_backward_workspace_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2,
+                                                          int32_t heads) {
+  if (B <= 0 || S <= 0 || C <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
+  const Dims m{B * C, S, B * C * S, D, F, U, H1, H2, heads};
+  Bump b(nullptr);
+  WorkAll w;
+  plan_work_all(b, w, m);
+  return b.off * sizeof(float) + 256;
+}
+
+int manner_hip_caum_train_all_backward(const float* const* params, const float* grad_scores, int64_t B, int64_t S, int64_t C, int32_t D, int32_t F,
+                                       int32_t U, int32_t H1, int32_t H2, int32_t heads, float p, const uint64_t* seeds, uint32_t site0, void* saved,
+                                       size_t saved_bytes, float* grad_x, float* grad_cand, float* const* grads, void* workspace,
+                                       size_t workspace_bytes, manner_hip_stream_t stream) {
+  int rc;
+  Dims m;
+  if ((rc = caum_train_all_check("caum_train_all_backward", B, S, C, D, F, U, H1, H2, heads, m))) return rc;
+  if (!(p >= 0.f && p < 1.f)) return fail(MANNER_HIP_E_INVALID, "caum_train_all_backward: p=%f outside [0, 1)", p);
+  if (!params || !grads) return fail(MANNER_HIP_E_INVALID, "caum_train_all_backward: null pointer");
+  for (int i = 0; i < P_COUNT; ++i)
+    if (!params[i] || !grads[i]) return fail(MANNER_HIP_E_INVALID, "caum_train_all_backward: null parameter or gradient %d", i);
+  hipStream_t s = (hipStream_t)stream;
+  const int FU = F + U, Si = (int)S, Ci = (int)C;
+  const size_t sizes[P_COUNT] = {(size_t)F * 4 * D, (size_t)F, (size_t)U * 2 * D, (size_t)U, (size_t)3 * U * U, (size_t)3 * U, (size_t)U * U, (size_t)U,
+                                 (size_t)U * FU, (size_t)U, (size_t)H1 * 2 * U, (size_t)H1, (size_t)H2 * H1, (size_t)H2, (size_t)H2, 1};
+  if (B == 0 || C == 0) {                          // no user or no column: the gradients are sums over nothing
+    for (int i = 0; i < P_COUNT; ++i) MANNER_HIP_TRY(hipMemsetAsync(grads[i], 0, sizes[i] * sizeof(float), s));
+    if (B > 0) {
+      if (!grad_x) return fail(MANNER_HIP_E_INVALID, "caum_train_all_backward: null pointer");
+      MANNER_HIP_TRY(hipMemsetAsync(grad_x, 0, (size_t)B * S * D * sizeof(float), s));
+    }
+    return MANNER_HIP_OK;
+  }
+  if (!grad_scores || !saved || !grad_x || !grad_cand || !workspace || (p > 0.f && !seeds))
+    return fail(MANNER_HIP_E_INVALID, "caum_train_all_backward: null pointer");
+  if (saved_bytes < manner_hip_caum_train_all_saved_bytes(B, S, C, D, F, U, H1, H2, heads))
+    return fail(MANNER_HIP_E_WORKSPACE, "caum_train_all_backward: saved buffer too small");
+  if (workspace_bytes < manner_hip_caum_train_all_backward_workspace_bytes(B, S, C, D, F, U, H1, H2, heads))
+    return fail(MANNER_HIP_E_WORKSPACE, "caum_train_all_backward: workspace too small");
+  Bump bs(saved), bw(workspace);
+  Saved sv;
+  WorkAll wa;
+  plan_saved(bs, sv, m);
+  plan_work_all(bw, wa, m);
+  Work& w = wa.w;
+  float* const part = wa.mpart;
+  float* const wt = wa.wt;
+  const int64_t R = m.R, P = m.B;
+  const Drop d1 = make_drop(0, site0, p), d2 = make_drop(0, site0 + 1, p), d3 = make_drop(0, site0 + 2, p);
+  const unsigned row_tiles = (unsigned)((R + CA_ROWS - 1) / CA_ROWS);
+  // the final dot, the weighted sum and the softmax per (user, column): ds (d score), wq (the weight of cd[b, c] in d all)
+  hipLaunchKernelGGL(user_kernel, dim3((unsigned)((P + CA_WAVES - 1) / CA_WAVES)), dim3(CA_BLOCK), 0, s, sv.score, sv.g, P, Si, (float*)nullptr, grad_scores,
+                     w.ds, w.wq);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tail_rows_kernel, dim3(row_tiles), dim3(CA_BLOCK), 0, s, w.ds, w.wq, params[P_WC], sv.d2, sv.cd, R, Si, H2, U, w.dt2, w.dall);
+  MANNER_LAUNCH_CHECK();
+  // dense_att.linear3: d wc = sum_r ds[r] t2[r]; d bc is zero in exact arithmetic (the softmax is shift-invariant)
+  if ((rc = launch_wgrad_all(w.ds, 1, sv.t2, R, H2, 1, part, grads[P_WC], H2, s))) return rc;
+  MANNER_HIP_TRY(hipMemsetAsync(grads[P_BC], 0, sizeof(float), s));
+  // dense_att.linear2
+  if ((rc = launch_wgrad_all(w.dt2, H2, sv.t1, R, H1, H2, part, grads[P_WB], H1, s))) return rc;
+  if ((rc = launch_colsum(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
+  if ((rc = launch_mdx(w.dt2, H2, params[P_WB], H1, R, H1, H2, nullptr, sv.d1, w.dt1, wt, s))) return rc;
+  // dense_att.linear: the history half over the rows, the candidate half over the (user, column) pairs (d ct[b, c] = sum_s d t1[b, c, s])
+  if ((rc = launch_wgrad_all(w.dt1, H1, sv.all, R, U, H1, part, grads[P_WA], 2 * U, s))) return rc;
+  if ((rc = launch_colsum(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
+  if ((rc = launch_mdx(w.dt1, H1, params[P_WA], 2 * U, R, U, H1, w.dall, nullptr, wa.dall2, wt, s))) return rc;
+  hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)P, (unsigned)((H1 + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.dt1, H1, 0,
+                     (const float*)nullptr, 0, (const float*)nullptr, Si, H1, d1, false, w.dct);
+  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_wgrad_all(w.dct, H1, sv.cd, P, D, H1, part, grads[P_WA] + U, 2 * U, s))) return rc;
+  // d cd[b, c] = dout[b, c] user[b, c] + d ct[b, c] Wa[:, U:] (the window and self-attention routes are added at the end)
+  hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)P, (unsigned)((U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, w.wq, sv.all, U, 0, (const float*)nullptr, 0,
+                     (const float*)nullptr, Si, U, d1, false, w.dcd);
+  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_mdx(w.dct, H1, params[P_WA] + U, 2 * U, P, D, H1, w.dcd, nullptr, wa.dcd2, wt, s))) return rc;
+  // linear3 and dropout3
+  if ((rc = launch_wgrad_all(wa.dall2, U, sv.cat, R, FU, U, part, grads[P_W3], FU, s))) return rc;
+  if ((rc = launch_colsum(wa.dall2, U, R, U, grads[P_B3], s))) return rc;
+  if ((rc = launch_mdx(wa.dall2, U, params[P_W3], FU, R, FU, U, nullptr, nullptr, w.dcat, wt, s))) return rc;
+  if (p > 0.f) {
+    hipLaunchKernelGGL(drop_cols_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, w.dcat, R * FU, Si, Ci, FU, d3, seeds);
+    MANNER_LAUNCH_CHECK();
+  }
+  // candi-selfatt: out-projection, attention, in-projection, linear2
+  if ((rc = launch_wgrad_all(w.dcat + F, FU, sv.att, R, U, U, part, grads[P_WOUT], U, s))) return rc;
+  if ((rc = launch_colsum(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
+  if ((rc = launch_mdx(w.dcat + F, FU, params[P_WOUT], U, R, U, U, nullptr, nullptr, w.datt, wt, s))) return rc;
+  if ((rc = launch_a0any_bwd_q(sv.qkv, sv.att, w.datt, w.dqkv, sv.stats, B, C * S, U, heads, s))) return rc;
+  if ((rc = launch_a0any_bwd_kv(sv.qkv, w.datt, sv.stats, w.dqkv, B, C * S, U, heads, s))) return rc;
+  if ((rc = launch_wgrad_all(w.dqkv, 3 * U, sv.h2, R, U, 3 * U, part, grads[P_WIN], U, s))) return rc;
+  if ((rc = launch_colsum(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
+  // the K third of d in_proj_bias is zero in exact arithmetic (a shift of every key moves every logit of a row alike)
+  MANNER_HIP_TRY(hipMemsetAsync(grads[P_BIN] + U, 0, (size_t)U * sizeof(float), s));
+  if ((rc = launch_mdx(w.dqkv, 3 * U, params[P_WIN], U, R, U, 3 * U, nullptr, nullptr, w.dh2, wt, s))) return rc;
+  if ((rc = launch_wgrad_all(w.dh2, U, sv.a2, R, 2 * D, U, part, grads[P_W2], 2 * D, s))) return rc;
+  if ((rc = launch_colsum(w.dh2, U, R, U, grads[P_B2], s))) return rc;
+  if ((rc = launch_mdx(w.dh2, U, params[P_W2], 2 * D, R, 2 * D, U, nullptr, nullptr, w.da2, wt, s))) return rc;
+  // candi-cnn: linear1 from cat[:, :F]
+  if ((rc = launch_wgrad_all(w.dcat, FU, sv.a1, R, 4 * D, F, part, grads[P_W1], 4 * D, s))) return rc;
+  if ((rc = launch_colsum(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
+  if ((rc = launch_mdx(w.dcat, FU, params[P_W1], 4 * D, R, 4 * D, F, nullptr, nullptr, w.da1, wt, s))) return rc;
+  // d x: per column the three windows and the self-attention operand through the column's dropout2, the columns added in ascending c;
+  // d cand: the sums over the slots, through the column's dropout1
+  hipLaunchKernelGGL(window_dx_cols_kernel, dim3((unsigned)(B * S)), dim3(CA_BLOCK), 0, s, w.da1, w.da2, Si, Ci, D, d2, seeds, grad_x);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cand_dx_cols_kernel, dim3((unsigned)P, (unsigned)((D + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, w.da1, w.da2, wa.dcd2, Si, Ci, D, d1,
+                     seeds, grad_cand);
+  MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }
 

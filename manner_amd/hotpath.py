@@ -90,20 +90,41 @@ def caum_forward(news_encoder, user_encoder, batch: Dict, dense: bool = True) ->
     [B, Cmax] with the reference's value in every slot: a zero-padded candidate row scores 0, a zero-padded history row takes part
     in every user's softmax.  No host synchronisation when the batch carries ``hist_max`` / ``cand_max``.  ``dense=False`` returns
     the real slots of that matrix as the ragged [sum c_i] vector (the padded rows still take part in the attention across the
-    users, as in the reference; the selection reads the count back to the host)."""
+    users, as in the reference; the selection reads the count back to the host).  With grad enabled and news rows that require grad
+    the dense tensors come from ``train.to_dense`` and the scores keep their graph into the rows (``dense=True`` only)."""
     nb =batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
     hip.status_poll(batch["batch_cand"].device)
     hist_vec = news_encoder(batch["x_hist"])
     cand_vec = news_encoder(batch["x_cand"])
     hist_off = segment_offsets(batch["batch_hist"], nb)
     cand_off = segment_offsets(batch["batch_cand"], nb)
-    hist_dense = hip.to_dense(hist_vec, hist_off, _width(batch, "hist_max", hist_off))
-    cand_dense = hip.to_dense(cand_vec, cand_off, _width(batch, "cand_max", cand_off), with_mask=not dense)
+    if dense and torch.is_grad_enabled() and (hist_vec.requires_grad or cand_vec.requires_grad):      # training: the rows keep their graph
+        hist_dense = train.to_dense(hist_vec, hist_off, _width(batch, "hist_max", hist_off))
+        cand_dense = train.to_dense(cand_vec, cand_off, _width(batch, "cand_max", cand_off))
+    else:
+        hist_dense = hip.to_dense(hist_vec, hist_off, _width(batch, "hist_max", hist_off))
+        cand_dense = hip.to_dense(cand_vec, cand_off, _width(batch, "cand_max", cand_off), with_mask=not dense)
     if not dense:
         cand_dense, real = cand_dense
     scores = user_encoder.forward_all(hist_dense, cand_dense)
     hip.status_arm(cand_vec.device)
     return scores if dense else scores[real]
+
+
+def caum_train_step(news_encoder, user_encoder, batch: Dict):
+    """CAUMPLMModule.model_step for training (reference baselines/caum_plm_module.py:174-189): ``forward`` through ``caum_forward`` —
+    the candidate loop as one ``forward_all`` call; with ``CAUMUserEncoder.train_all_columns`` set, one library call forward and one
+    backward for all columns — then ``nn.CrossEntropyLoss(scores, y_true)`` on the dense zero-padded rows, computed by
+    ``train.model_step_loss(supcon=False, c_max=...)`` from the real slots: a zero-padded candidate row scores exactly 0 with or without
+    dropout, the padded zero that loss mode puts into the softmax.  No host synchronisation when the batch carries ``hist_max`` /
+    ``cand_max``.  Returns (loss, ragged scores [sum c_i] detached, cand_off) — call ``loss.backward()`` and step the optimiser."""
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    cand_off = segment_offsets(batch["batch_cand"], nb)
+    c_max = _width(batch, "cand_max", cand_off)
+    dense = caum_forward(news_encoder, user_encoder, dict(batch, cand_max=c_max), dense=True)
+    ragged = dense.reshape(-1).index_select(0, train.dense_slots(cand_off, int(batch["batch_cand"].numel()), c_max))
+    loss, _ = train.model_step_loss(ragged, batch["labels"].to(torch.float32), cand_off, supcon=False, c_max=c_max)
+    return loss, ragged.detach(), cand_off
 
 
 def _cat_tokens(a: Dict, b: Dict, pad_id: int) -> Dict:

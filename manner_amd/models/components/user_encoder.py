@@ -98,7 +98,12 @@ class CAUMUserEncoder(nn.Module):
     cat[all (U), candidate (D)]: as in the reference only D == U can run; construction stays legal, ``forward`` refuses D != U.
     f32 whatever the autocast state.  The three dropouts are on in train() only and draw one seed per call from torch's CPU generator
     (sites 7, 8, 9 of the counter-based generator).  ``forward_all`` takes the whole dense candidate tensor [B, C, D]: at evaluation
-    time it is one library call for all C columns, otherwise the reference's loop over ``forward``."""
+    time it is one library call for all C columns, otherwise the reference's loop over ``forward`` — or, with ``train_all_columns`` set,
+    one training call for all columns."""
+
+    #: opt-in: ``forward_all`` in train() (dropout on, or a graph recorded) as ONE ``train.caum_scores_all`` call over all columns
+    #: instead of the loop over ``forward`` — the same seed draws and masks; sums in another order, so not the loop's bits
+    train_all_columns = False
 
     def __init__(self, news_vector_dim: int, num_filters: int, dense_att_hidden_dim1: int, dense_att_hidden_dim2: int, user_vector_dim: int,
                  num_attention_heads: int, dropout_probability: float) -> None:
@@ -137,8 +142,20 @@ class CAUMUserEncoder(nn.Module):
         Without dropout and with nothing to differentiate (eval() under no_grad / inference_mode, or frozen weights and inputs) it is
         one library call that takes every history-only and candidate-only product once (``hip.caum_scores_all``).  In train() with
         p > 0 the reference draws fresh masks of the clicked news per column, and a recorded graph needs the per-column backward:
-        then it is that loop itself over ``forward`` — the same seed draws, bits and gradients as the loop written by hand."""
+        then it is that loop itself over ``forward`` — the same seed draws, bits and gradients as the loop written by hand.  With the
+        class attribute ``train_all_columns`` set, that case is one ``train.caum_scores_all`` call instead: one seed per column drawn
+        exactly as the loop draws them (the CPU generator ends in the same state, the masks are the same), the C columns as rows of
+        one forward and one backward on the matrix cores."""
         p = self.dropout1.p if self.training else 0.0
+        if self.train_all_columns and (p > 0.0 or _differentiable(self, clicked_news_vector, cand_news_vector)):
+            mha = self.multihead_attention
+            if mha.dropout != 0.0:
+                raise RuntimeError("attention-probability dropout inside nn.MultiheadAttention is not built (the reference uses 0)")
+            if len({self.dropout1.p, self.dropout2.p, self.dropout3.p}) != 1:
+                raise RuntimeError("CAUMUserEncoder: the three dropouts share one probability in the reference; differing ones are not built")
+            # the loop's own draws, one per column in column order (none at p == 0): the CPU generator ends where the loop leaves it
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(cand_news_vector.shape[1])] if p > 0.0 else None
+            return train.caum_scores_all(clicked_news_vector, cand_news_vector, self._params(), mha.num_heads, p=p, seeds=seeds)
         if p > 0.0 or _differentiable(self, clicked_news_vector, cand_news_vector):
             scores = torch.zeros(cand_news_vector.shape[0], cand_news_vector.shape[1], device=cand_news_vector.device)
             scores = scores.transpose(1, 0)

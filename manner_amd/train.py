@@ -705,6 +705,99 @@ def caum_user_scores(x: Tensor, c: Tensor, params: Sequence[Tensor], heads: int,
     return _CaumUser.apply(x, c, opts, *params)
 
 
+def dense_slots(off: Tensor, n: int, width: int) -> Tensor:
+    """The flat slot b * width + j of each of the ``n`` ragged rows in the dense [B, width] layout of ``to_dense_batch`` — from the
+    offsets on the device, nothing read back."""
+    rows = torch.arange(n, dtype=torch.int64, device=off.device)
+    seg = torch.searchsorted(off[1:].contiguous(), rows, right=True)
+    return seg * int(width) + (rows - off[seg])
+
+
+class _ToDense(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, off: Tensor, width: int):
+        ctx.save_for_backward(off)
+        ctx.n, ctx.width = x.shape[0], int(width)
+        return hip.to_dense(x, off, int(width))
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (off,) = ctx.saved_tensors
+        g = g.contiguous()
+        return g.reshape((-1,) + tuple(g.shape[2:])).index_select(0, dense_slots(off, ctx.n, ctx.width)), None, None
+
+
+def to_dense(x: Tensor, off: Tensor, width: int) -> Tensor:
+    """``hip.to_dense`` (K9, ``to_dense_batch``) with autograd into the ragged rows: the gradient of a real slot, none for the padding."""
+    return _ToDense.apply(_f32(x, "x"), hip._dev(off, torch.int64, "off").contiguous(), int(width))
+
+
+class _CaumAll(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, cand: Tensor, opts: dict, seeds: Optional[Tensor], *params: Tensor):
+        b, s, c = opts["dims"][:3]
+        lib = _lib.load()
+        scores = torch.empty((b, c), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            need = int(lib.manner_hip_caum_train_all_saved_bytes(*opts["dims"]))
+            saved = hip._workspace(need, x.device)
+            _lib.check(lib.manner_hip_caum_train_all_forward(hip._ptr(x), hip._ptr(cand), _table([t.detach() for t in params]), *opts["dims"],
+                                                             C.c_float(opts["p"]), hip._ptr(seeds), C.c_uint32(opts["site0"]), hip._ptr(scores),
+                                                             hip._ptr(saved), need, hip._stream()))
+        ctx.opts, ctx.saved_buf, ctx.saved_bytes, ctx.seeds = opts, saved, need, seeds
+        ctx.save_for_backward(*params)
+        return scores
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        params = ctx.saved_tensors
+        opts = ctx.opts
+        dims = opts["dims"]
+        b, s, c, d = dims[:4]
+        dev = ctx.saved_buf.device
+        lib = _lib.load()
+        dx = torch.empty((b, s, d), dtype=torch.float32, device=dev)
+        dc = torch.empty((b, c, d), dtype=torch.float32, device=dev)
+        grads = [torch.empty_like(t) for t in params]
+        with torch.cuda.device(dev):
+            g = _f32(g, "grad")
+            need = int(lib.manner_hip_caum_train_all_backward_workspace_bytes(*dims))
+            ws = hip._workspace(need, dev)
+            _lib.check(lib.manner_hip_caum_train_all_backward(_table([t.detach() for t in params]), hip._ptr(g), *dims, C.c_float(opts["p"]),
+                                                              hip._ptr(ctx.seeds), C.c_uint32(opts["site0"]), hip._ptr(ctx.saved_buf),
+                                                              ctx.saved_bytes, hip._ptr(dx), hip._ptr(dc), _table(grads), hip._ptr(ws), need,
+                                                              hip._stream()))
+        return (dx, dc, None, None, *grads)
+
+
+def caum_scores_all(x: Tensor, cand: Tensor, params: Sequence[Tensor], heads: int, p: float = 0.0, seeds: Optional[Sequence[int]] = None,
+                    site0: int = hip.CAUM_DROPOUT_SITE) -> Tensor:
+    """The candidate loop of CAUMPLMModule.forward in train(): x [B, S, D], cand [B, C, D] -> scores [B, C] with autograd into x, cand
+    and the 16 parameters, column c what ``caum_user_scores(x, cand[:, c, :], ..., p, seeds[c], site0)`` computes — the same dropout
+    sites and element indices, so the same masks — in ONE library call forward and one backward over the B C S rows (f32 matrix-core
+    linears, data and weight gradients).  ``seeds``: C integers (or an int64 tensor), needed when ``p`` > 0; they reach the device as one
+    small tensor, nothing is read back.  d x is the sum of the columns' contributions in ascending c, each through its own dropout2
+    mask; the two analytically zero gradients come back as exact zeros."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 3:
+        raise ValueError(f"caum_scores_all: cand_news_vector {tuple(getattr(cand, 'shape', ()))} must be [B, C, D]")
+    b, c = cand.shape[0], cand.shape[1]
+    x, _, params, dims = hip._caum_operands(x, cand[:, 0, :] if c else cand.new_empty((b, cand.shape[2])), params, heads)
+    cand = hip._dev(cand, torch.float32, "cand_news_vector").contiguous()
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"caum_scores_all: p={p} outside [0, 1)")
+    dev_seeds = None
+    if float(p) > 0.0:
+        if seeds is None or len(seeds) != c:
+            raise ValueError(f"caum_scores_all: p > 0 needs one seed per candidate column ({c})")
+        if isinstance(seeds, torch.Tensor):
+            dev_seeds = seeds.to(device=x.device, dtype=torch.int64).contiguous()
+        else:                                                   # any 64 bits, carried as int64
+            wrapped = [((int(v) & (2 ** 64 - 1)) ^ (1 << 63)) - (1 << 63) for v in seeds]
+            dev_seeds = torch.tensor(wrapped, dtype=torch.int64).to(x.device, non_blocking=True)
+    opts = dict(dims=(dims[0], dims[1], c) + dims[2:], p=float(p), site0=int(site0))
+    return _CaumAll.apply(x, cand, opts, dev_seeds, *params)
+
+
 def _gru_backward(ctx, g: Tensor, want_h0: bool):
     """manner_hip_gru_backward from the buffers ``ctx`` kept: g [B, >= H] (its first H columns are d last_hidden) ->
     (dx, dh0 or None, [dw_ih, dw_hh, db_ih, db_hh])."""
