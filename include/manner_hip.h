@@ -658,6 +658,43 @@ int manner_hip_bmm(const float* a, const float* b, int64_t B, int64_t M, int64_t
 int manner_hip_bmm_backward(const float* grad_out, const float* a, const float* b, int64_t B, int64_t M, int64_t N, int32_t D, int64_t b_stride_b,
                             int64_t b_stride_d, int64_t b_stride_n, float* grad_a, float* grad_b, manner_hip_stream_t stream);
 
+/* ---- MINERModule's own lines (csrc/miner.hip; f32; additive exports) --------------------------------------------------------------
+ * What baselines/miner_module.py:153-242 computes between the operators above, without the [N_hist, N_cand] cosine matrix, the
+ * [B, S, N_cand] dense bias, the per-impression host loop, the [B, C, K] product and the [B, K, K] Gram matrix.
+ * manner_hip_miner_category_bias (miner_module.py:162-181 with attention.py:75): hist_cat int64 [N_hist], cand_cat int64 [T], the frozen
+ * category table f32 [V, Dc], hist_off / cand_off int64 [B + 1]; bias f32 [B, S] (hand it to manner_hip_poly_attention as [B, S, 1],
+ * T = 1) with bias[b, s] = (1 / T) sum over the candidates t of the batch that are NOT user b's own of cos(x_{b,s}, y_t) — T counts
+ * ALL candidates, the own columns are zeroed and still counted, cos divides by the norms themselves (torchmetrics: no epsilon, so an
+ * all-zero row gives NaN wherever it is summed), a padded slot s >= h_b and an empty exclusion set are exactly 0.  The unit candidate
+ * rows outside the user's own are summed directly in ascending t, then one dot product per slot.  p > 0: nn.Dropout on the embedded
+ * rows by the counter rule of the training path, element (row of its side) * Dc + d, history at (seed_hist, site_hist), candidates at
+ * (seed_cand, site_cand).  Dc <= 1024, S <= 256 (MANNER_HIP_E_INVALID otherwise); a category id outside [0, V) is never read and raises
+ * MANNER_HIP_STATUS_INDEX in `status` (may be NULL).  No gradient: the embedding is frozen.
+ * manner_hip_miner_code_scores (miner_module.py:195-202): cand [N, D] ragged by cand_off [B + 1], user [B, K, D]; out [N] =
+ * max_k (mode 0) or mean_k (mode 1) of cand[t] . user[b, k] — the dot products and the reduction in one kernel.  argmax int32 [N] (may be
+ * NULL; mode 0) receives the winning code, ties to the LOWEST index (torch's max(dim) on the CPU).  _backward: grad_cand [N, D] and
+ * grad_user [B, K, D] from grad_out [N]: to the argmax code (mode 0, `argmax` of the forward) or spread evenly over the K codes (mode
+ * 1); grad_user is a sum over the user's candidates in ascending order.  K <= 64, D <= 1024.
+ * manner_hip_disagreement_loss (miner_module.py:237-241, components/utils.py:4-31 with zero_diagonal=True, then .mean()): user
+ * [B, K, D] -> loss [1] = (1 / (B K K)) sum_b sum_{i != j} u_i . u_j, u = x / (1e-8 + ||x||) (a zero row is 0).  workspace: 8-byte
+ * aligned.  _backward: grad_user [B, K, D] from the DEVICE scalar grad_loss [1]; a zero row gets the finite gradient through 1 / 1e-8
+ * that torch autograd gives.  K <= 64, D <= 1024.  Every reduction has a fixed order (no floating-point atomics). */
+size_t manner_hip_miner_category_bias_workspace_bytes(int64_t n_hist, int64_t T, int64_t B, int32_t Dc);
+int manner_hip_miner_category_bias(const int64_t* hist_cat, const int64_t* cand_cat, const float* table, int64_t V, int32_t Dc,
+                                   const int64_t* hist_off, const int64_t* cand_off, int64_t n_hist, int64_t T, int64_t B, int64_t S, float p,
+                                   uint64_t seed_hist, uint64_t seed_cand, uint32_t site_hist, uint32_t site_cand, float* bias, void* workspace,
+                                   size_t workspace_bytes, int32_t* status, manner_hip_stream_t stream);
+int manner_hip_miner_code_scores(const float* cand, const int64_t* cand_off, const float* user, int64_t N, int64_t B, int32_t K, int32_t D,
+                                 int32_t mode, float* out, int32_t* argmax, manner_hip_stream_t stream);
+int manner_hip_miner_code_scores_backward(const float* grad_out, const float* cand, const int64_t* cand_off, const float* user,
+                                          const int32_t* argmax, int64_t N, int64_t B, int32_t K, int32_t D, int32_t mode, float* grad_cand,
+                                          float* grad_user, manner_hip_stream_t stream);
+size_t manner_hip_disagreement_loss_workspace_bytes(int64_t B);
+int manner_hip_disagreement_loss(const float* user, int64_t B, int32_t K, int32_t D, float* loss, void* workspace, size_t workspace_bytes,
+                                 manner_hip_stream_t stream);
+int manner_hip_disagreement_loss_backward(const float* user, const float* grad_loss, int64_t B, int32_t K, int32_t D, float* grad_user,
+                                          manner_hip_stream_t stream);
+
 /* ---- the CAUM baseline's operators (csrc/caum.hip; f32, forward and backward; additive exports) -------------------------------------
  * manner_hip_axis0_attention_any is manner_hip_axis0_attention at ANY head dim 1 <= E / heads <= 64 (CAUM ships 25 and 5): qkv
  * [L0, B1, 3E] -> out [L0, B1, E], attention along axis 0.  stats [L0 * B1 * heads * 3] (may be NULL in the forward) receives the

@@ -164,6 +164,14 @@ SIGNATURES = {
     "manner_hip_axis0_attention_wide": (C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _P, _P]),
     "manner_hip_axis0_attention_wide_backward_q": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _P]),
     "manner_hip_axis0_attention_wide_backward_kv": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P]),
+    "manner_hip_miner_category_bias_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I32]),
+    "manner_hip_miner_category_bias": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _I64, _I64, _I64, _I64, C.c_float, C.c_uint64, C.c_uint64,
+                                                 C.c_uint32, C.c_uint32, _P, _P, _SZ, _P, _P]),
+    "manner_hip_miner_code_scores": (C.c_int, [_P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "manner_hip_miner_code_scores_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "manner_hip_disagreement_loss_workspace_bytes": (_SZ, [_I64]),
+    "manner_hip_disagreement_loss": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
+    "manner_hip_disagreement_loss_backward": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 
 _lib = None

@@ -60,8 +60,10 @@ news encoder builds the category encoder):
 ``install(baselines=("naml_plm",))`` (configs/model/naml_plm.yaml; naml_mind) rebinds the two news-side classes alone — NAML-PLM's user
 encoder, ``NAMLUserEncoder``, is bound by every install.  ``MINSPLMModule`` / ``NAMLPLMModule``'s own lines stay the reference's torch.
 
-``MINERModule`` itself is not mirrored: its category-bias construction, ``pairwise_cosine_similarity``, the max / mean aggregation
-and the disagreement loss are Lightning-level code and stay the reference's torch.  A plain ``install()`` binds exactly the first
+``MINERModule`` itself is not rebound, and the unchanged module keeps its torch lines; its category-bias construction, the max / mean
+aggregation and the disagreement loss are built as ``hotpath.miner_forward`` / ``hotpath.miner_train_step`` (csrc/miner.hip) for a
+``forward`` / ``model_step`` that delegates to them.  What stays the reference's torch: the metrics
+bookkeeping of ``model_step`` and the Lightning hooks.  A plain ``install()`` binds exactly the first
 table, whatever an earlier call added stays until ``uninstall()``.
 
 Use (no reference source line changes):

@@ -806,6 +806,90 @@ def bmm(a: Tensor, b: Tensor) -> Tensor:
     return out
 
 
+MINER_DROPOUT_SITE = 12   # category_dropout of MINERModule: history rows at site 12, candidate rows at 13 (11 is LSTUR's)
+MINER_SCORE_MODES = {"max": 0, "mean": 1}
+
+
+def miner_category_bias(hist_cat: Tensor, cand_cat: Tensor, table: Tensor, hist_off: Tensor, cand_off: Tensor, width: int, p: float = 0.0,
+                        seeds: Sequence[int] = (0, 0), site0: int = MINER_DROPOUT_SITE) -> Tensor:
+    """The category bias of MINERModule.forward (reference baselines/miner_module.py:162-181) reduced to what PolyAttention keeps of it
+    (attention.py:75, the mean over its last axis): hist_cat int64 [N_hist], cand_cat int64 [T], the frozen ``category_embedding.weight``
+    [V, Dc], hist_off / cand_off int64 [B + 1], ``width`` = S -> bias [B, S, 1], bias[b, s] = (1 / T) sum over the candidates of the
+    batch that are not user b's own of cos(x_{b,s}, y_t) — the reference's value, quirks included: T counts every candidate, the cosine
+    has no epsilon (a zero row gives NaN where it is summed), padded slots are exactly 0.  Hand it to ``poly_attention`` as ``bias``.
+    ``p`` > 0: ``category_dropout`` in train(), history rows at (seeds[0], site0), candidate rows at (seeds[1], site0 + 1).
+    Dc <= 1024, S <= 256; a category id outside the table raises at ``check_status``.  No gradient (the embedding is frozen)."""
+    hist_cat = _dev(hist_cat, torch.int64, "x_hist.category").contiguous().reshape(-1)
+    cand_cat = _dev(cand_cat, torch.int64, "x_cand.category").contiguous().reshape(-1)
+    table = _dev(table, torch.float32, "category_embedding.weight").contiguous()
+    hist_off = _dev(hist_off, torch.int64, "hist_off").contiguous()
+    cand_off = _dev(cand_off, torch.int64, "cand_off").contiguous()
+    assert table.dim() == 2 and hist_off.numel() == cand_off.numel() >= 1
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"miner_category_bias: p={p} outside [0, 1)")
+    b, (v, dc) = hist_off.numel() - 1, table.shape
+    nh, t = hist_cat.numel(), cand_cat.numel()
+    bias = torch.empty((b, int(width), 1), dtype=torch.float32, device=table.device)
+    lib = _lib.load()
+    with torch.cuda.device(table.device):
+        need = int(lib.manner_hip_miner_category_bias_workspace_bytes(nh, t, b, dc))
+        ws = _workspace(need, table.device)
+        _lib.check(lib.manner_hip_miner_category_bias(_ptr(hist_cat), _ptr(cand_cat), _ptr(table), v, dc, _ptr(hist_off), _ptr(cand_off), nh, t, b,
+                                                      int(width), C.c_float(p), C.c_uint64(int(seeds[0]) & (2 ** 64 - 1)),
+                                                      C.c_uint64(int(seeds[1]) & (2 ** 64 - 1)), C.c_uint32(site0), C.c_uint32(site0 + 1),
+                                                      _ptr(bias), _ptr(ws), need, _ptr(device_status(table.device).word), _stream()))
+    return bias
+
+
+def _code_scores_operands(cand: Tensor, cand_off: Tensor, user: Tensor, score_type: str):
+    if score_type not in MINER_SCORE_MODES:
+        raise ValueError(f"miner_code_scores: score_type {score_type!r} ('max' or 'mean'; 'weighted' goes through target_attention)")
+    cand = _dev(cand, torch.float32, "candidate_news_vector").contiguous()
+    user = _dev(user, torch.float32, "user_vector").contiguous()
+    cand_off = _dev(cand_off, torch.int64, "cand_off").contiguous()
+    assert cand.dim() == 2 and user.dim() == 3 and user.shape[2] == cand.shape[1] and cand_off.numel() == user.shape[0] + 1
+    return cand, cand_off, user, MINER_SCORE_MODES[score_type]
+
+
+def _code_scores_forward(cand: Tensor, cand_off: Tensor, user: Tensor, mode: int, arg: Optional[Tensor]) -> Tensor:
+    n, d = cand.shape
+    b, k = user.shape[:2]
+    out = torch.empty(n, dtype=torch.float32, device=cand.device)
+    with torch.cuda.device(cand.device):
+        _lib.check(_lib.load().manner_hip_miner_code_scores(_ptr(cand), _ptr(cand_off), _ptr(user), n, b, k, d, mode, _ptr(out), _ptr(arg),
+                                                            _stream()))
+    return out
+
+
+def miner_code_scores(cand: Tensor, cand_off: Tensor, user: Tensor, score_type: str) -> Tensor:
+    """The score lines of MINERModule.forward for ``score_type`` 'max' / 'mean' (reference baselines/miner_module.py:195-202) on the ragged
+    candidate rows: cand [N, D], cand_off int64 [B + 1], user [B, K, D] -> [N], max_k or mean_k of cand[t] . user[b, k] — no [B, C, K]
+    tensor and no dense candidates (a zero-padded row would score exactly 0).  K <= 64, D <= 1024."""
+    cand, cand_off, user, mode = _code_scores_operands(cand, cand_off, user, score_type)
+    return _code_scores_forward(cand, cand_off, user, mode, None)
+
+
+def _disagreement_operand(user: Tensor) -> Tensor:
+    user = _dev(user, torch.float32, "user_vector").contiguous()
+    assert user.dim() == 3
+    return user
+
+
+def disagreement_loss(user: Tensor) -> Tensor:
+    """MINER's disagreement loss (reference baselines/miner_module.py:237-241: ``pairwise_cosine_similarity(u, u, zero_diagonal=True)
+    .mean()``, components/utils.py:4-31): user [B, K, D] -> scalar, the off-diagonal cosines with the reference's 1e-8 + norm,
+    divided by B K K.  K <= 64, D <= 1024."""
+    user = _disagreement_operand(user)
+    b, k, d = user.shape
+    loss = torch.empty(1, dtype=torch.float32, device=user.device)
+    lib = _lib.load()
+    with torch.cuda.device(user.device):
+        need = int(lib.manner_hip_disagreement_loss_workspace_bytes(b))
+        ws = _workspace(need, user.device)
+        _lib.check(lib.manner_hip_disagreement_loss(_ptr(user), b, k, d, _ptr(loss), _ptr(ws), need, _stream()))
+    return loss[0]
+
+
 def axis0_attention_any(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
     """The attention core of ``mha_axis0_any`` on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]; ``stats`` f32 [L0 * B1 * heads * 3]
     receives the softmax statistics the backward reads."""

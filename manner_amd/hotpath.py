@@ -5,6 +5,8 @@
   (reference manner/models/ensemble_module.py:95-151) on the fused HIP kernels, returning the same
   dense ``[B, Cmax]`` score matrix (padded slots: 0 for the CR-Module, the z-scored zero for the ensemble)
   — mode R of SURVEY.md §8d: every history and candidate occurrence is encoded.
+* ``caum_forward`` / ``caum_train_step`` and ``miner_forward`` / ``miner_train_step`` do the same for ``CAUMPLMModule`` and
+  ``MINERModule`` (reference manner/models/baselines/): the module's own lines between the mirrored leaf classes.
 * ``encode_table`` / ``score_impressions`` are the table architecture (mode T): each unique news is
   encoded once per module into ``[N_news, D]``, impressions are scored by index.  Valid for
   ``use_entities=False`` only.
@@ -169,6 +171,92 @@ def cr_train_step(news_encoder, batch: Dict, supcon: bool = True, temperature: f
     loss, _ = train.model_step_loss(scores, batch["labels"].to(torch.float32), cand_off, supcon=supcon, temperature=temperature,
                                     c_max=c_max)
     return loss, scores.detach(), cand_off
+
+
+def _miner_scores(hist_vec: Tensor, cand_vec: Tensor, user_encoder, batch: Dict, nb: int, score_type: str, target_aware_attn,
+                  category_embedding, category_dropout):
+    """The lines of MINERModule.forward below its two encoder calls (reference baselines/miner_module.py:156-212) ->
+    (user_vector [B, K, D], ragged scores [sum c_i], cand_off, Cmax or None when nothing needed it)."""
+    if score_type not in ("max", "mean", "weighted"):
+        raise ValueError("Invalid method of aggregating scores.")
+    hist_off = segment_offsets(batch["batch_hist"], nb)
+    cand_off = segment_offsets(batch["batch_cand"], nb)
+    s = _width(batch, "hist_max", hist_off)
+    graph = torch.is_grad_enabled() and (hist_vec.requires_grad or cand_vec.requires_grad)
+    hist_dense = (train.to_dense if graph else hip.to_dense)(hist_vec, hist_off, s)
+    mask_hist = torch.arange(s, device=hist_off.device)[None, :] < (hist_off[1:] - hist_off[:-1])[:, None]
+    bias = None
+    if category_embedding is not None:
+        p = float(category_dropout.p) if category_dropout is not None and category_dropout.training else 0.0
+        # the mirrors' seed draw on torch's CPU generator, history first; none at p = 0 or in eval()
+        seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(2)] if p > 0.0 else (0, 0)
+        bias = hip.miner_category_bias(batch["x_hist"]["category"], batch["x_cand"]["category"], category_embedding.weight.detach(), hist_off,
+                                       cand_off, s, p=p, seeds=seeds)
+    user_vector = user_encoder(clicked_news_vector=hist_dense, attn_mask=mask_hist, bias=bias)
+    c_max = None
+    if score_type == "weighted":
+        if target_aware_attn is None:
+            raise ValueError("score_type 'weighted' needs target_aware_attn")
+        c_max = _width(batch, "cand_max", cand_off)
+        grad_on = torch.is_grad_enabled()
+        cand_dense = (train.to_dense if grad_on and cand_vec.requires_grad else hip.to_dense)(cand_vec, cand_off, c_max)
+        rows = user_vector.permute(0, 2, 1)
+        value = train.bmm(cand_dense, rows) if grad_on and (cand_dense.requires_grad or user_vector.requires_grad) else hip.bmm(cand_dense, rows)
+        dense = target_aware_attn(query=user_vector, key=cand_dense, value=value)
+        ragged = dense.reshape(-1).index_select(0, train.dense_slots(cand_off, int(batch["batch_cand"].numel()), c_max))
+    elif torch.is_grad_enabled() and (cand_vec.requires_grad or user_vector.requires_grad):
+        ragged = train.miner_code_scores(cand_vec, cand_off, user_vector, score_type)
+    else:
+        ragged = hip.miner_code_scores(cand_vec, cand_off, user_vector, score_type)
+    return user_vector, ragged, cand_off, c_max
+
+
+def _miner_dense(ragged: Tensor, cand_off: Tensor, width: int) -> Tensor:
+    return (train.to_dense if torch.is_grad_enabled() and ragged.requires_grad else hip.to_dense)(ragged, cand_off, width)
+
+
+def miner_forward(news_encoder, user_encoder, batch: Dict, *, score_type: str, target_aware_attn=None, category_embedding=None,
+                  category_dropout=None, dense: bool = True):
+    """MINERModule.forward (reference baselines/miner_module.py:153-212) -> (user_vector [B, K, D], scores): the two news-encoder calls on
+    ``batch["x_hist"]["text"]`` / ``batch["x_cand"]["text"]``, the history to dense with its mask, the category bias as ONE
+    ``hip.miner_category_bias`` call when ``category_embedding`` (the frozen nn.Embedding) is given — ``category_dropout`` is the
+    module's nn.Dropout, its ``.p`` and ``.training`` are read — ``user_encoder`` (the PolyAttention of this package), and the scores:
+    'max' / 'mean' by ``miner_code_scores`` on the ragged rows, 'weighted' through to_dense -> bmm -> ``target_aware_attn``.
+    ``dense=True`` returns [B, Cmax] with padded slots exactly 0 (a zero-padded candidate row scores 0 under all three types),
+    ``dense=False`` the ragged [sum c_i] vector.  No host synchronisation when the batch carries ``hist_max`` / ``cand_max``."""
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    hist_vec = news_encoder(batch["x_hist"]["text"])
+    cand_vec = news_encoder(batch["x_cand"]["text"])
+    user_vector, ragged, cand_off, c_max = _miner_scores(hist_vec, cand_vec, user_encoder, batch, nb, score_type, target_aware_attn,
+                                                        category_embedding, category_dropout)
+    hip.status_arm(cand_vec.device)
+    if not dense:
+        return user_vector, ragged
+    return user_vector, _miner_dense(ragged, cand_off, c_max if c_max is not None else _width(batch, "cand_max", cand_off))
+
+
+def miner_train_step(news_encoder, user_encoder, batch: Dict, *, score_type: str, target_aware_attn=None, category_embedding=None,
+                     category_dropout=None):
+    """The loss lines of MINERModule.model_step (reference baselines/miner_module.py:226-242): ``forward`` as ``miner_forward`` — with both
+    news sets through ONE encoder call — then ``nn.CrossEntropyLoss(scores [B, Cmax], y_true)`` from the ragged scores
+    (``train.model_step_loss(supcon=False, c_max=...)`` supplies the padded zeros) plus ``train.disagreement_loss(user_vector)``.
+    Returns (loss, ragged scores [sum c_i] detached, cand_off) — call ``loss.backward()`` and step the optimiser.  The metrics
+    bookkeeping of ``model_step`` (preds / targets / sizes per impression) is the caller's."""
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    # one encoder call for both sets, as encode_hist_and_cand (MINERNewsEncoder takes the token dict itself and holds the PLM directly)
+    th, tc = batch["x_hist"]["text"], batch["x_cand"]["text"]
+    cfg = getattr(getattr(news_encoder, "plm_model", None), "cfg", None)
+    both = news_encoder(_cat_tokens(th, tc, cfg.pad_id if cfg is not None else 0))
+    hist_vec, cand_vec = both[:th["input_ids"].shape[0]], both[th["input_ids"].shape[0]:]
+    user_vector, ragged, cand_off, c_max = _miner_scores(hist_vec, cand_vec, user_encoder, batch, nb, score_type, target_aware_attn,
+                                                        category_embedding, category_dropout)
+    hip.status_arm(cand_vec.device)
+    if c_max is None:
+        c_max = _width(batch, "cand_max", cand_off)
+    ce, _ = train.model_step_loss(ragged, batch["labels"].to(torch.float32), cand_off, supcon=False, c_max=c_max)
+    return ce + train.disagreement_loss(user_vector), ragged.detach(), cand_off
 
 
 def a_train_step(news_encoder, batch: Dict, temperature: float = 0.1):

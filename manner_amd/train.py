@@ -600,6 +600,59 @@ def target_attention(query: Tensor, key: Tensor, value: Tensor, lin_w: Tensor) -
     return _TargetAttention.apply(_f32(query, "query"), _f32(key, "key"), _f32(value, "value"), _f32(lin_w, "linear.weight"))
 
 
+class _CodeScores(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cand: Tensor, cand_off: Tensor, user: Tensor, mode: int):
+        arg = torch.empty(cand.shape[0], dtype=torch.int32, device=cand.device) if mode == 0 else None
+        out = hip._code_scores_forward(cand, cand_off, user, mode, arg)
+        ctx.save_for_backward(cand, cand_off, user, arg)
+        ctx.mode = mode
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        cand, cand_off, user, arg = ctx.saved_tensors
+        n, d = cand.shape
+        b, k = user.shape[:2]
+        dc, du = torch.empty_like(cand), torch.empty_like(user)
+        with torch.cuda.device(cand.device):
+            g = _f32(g, "grad")
+            _lib.check(_lib.load().manner_hip_miner_code_scores_backward(hip._ptr(g), hip._ptr(cand), hip._ptr(cand_off), hip._ptr(user), hip._ptr(arg),
+                                                                         n, b, k, d, ctx.mode, hip._ptr(dc), hip._ptr(du), hip._stream()))
+        return dc, None, du, None
+
+
+def miner_code_scores(cand: Tensor, cand_off: Tensor, user: Tensor, score_type: str) -> Tensor:
+    """``hip.miner_code_scores`` with autograd into the candidate rows and the user vectors: 'max' sends a candidate's gradient to its
+    argmax code (ties: the lowest index, as torch's CPU ``max(dim)``), 'mean' spreads it evenly over the K codes; d user is a
+    fixed-order sum over the user's candidates."""
+    cand, cand_off, user, mode = hip._code_scores_operands(cand, cand_off, user, score_type)
+    return _CodeScores.apply(cand, cand_off, user, mode)
+
+
+class _Disagreement(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, user: Tensor):
+        ctx.save_for_backward(user)
+        return hip.disagreement_loss(user)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (user,) = ctx.saved_tensors
+        b, k, d = user.shape
+        du = torch.empty_like(user)
+        with torch.cuda.device(user.device):
+            g = _f32(g, "grad").reshape(1)                       # stays on the device: nothing is read back
+            _lib.check(_lib.load().manner_hip_disagreement_loss_backward(hip._ptr(user), hip._ptr(g), b, k, d, hip._ptr(du), hip._stream()))
+        return du
+
+
+def disagreement_loss(user: Tensor) -> Tensor:
+    """``hip.disagreement_loss`` with autograd into user [B, K, D]; a zero row receives the finite gradient through 1 / 1e-8 that torch
+    autograd gives the reference's lines."""
+    return _Disagreement.apply(hip._disagreement_operand(user))
+
+
 class _Axis0Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv: Tensor, heads: int):
