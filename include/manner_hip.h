@@ -695,6 +695,50 @@ int manner_hip_disagreement_loss(const float* user, int64_t B, int32_t K, int32_
 int manner_hip_disagreement_loss_backward(const float* user, const float* grad_loss, int64_t B, int32_t K, int32_t D, float* grad_user,
                                           manner_hip_stream_t stream);
 
+/* ---- the auxiliary heads and losses of TANR-PLM and SentiRec-PLM (csrc/aspect.hip; f32; additive exports) -------------------------
+ * What baselines/tanr_plm_module.py:139-141,172-177 and baselines/sentirec_plm_module.py:141-143,174-193 compute over the news rows of a
+ * batch, without the torch.cat, the one-hot matrix, the dense [B, Cmax] blocks and the per-impression host loop.
+ * manner_hip_head_ce: x [N, D], w [O, D], b [O], target int64 [N] (plain class indices) -> loss [1] = the mean over the N rows of
+ * -log softmax(x w^T + b)[target]: nn.Linear, the row softmax, the log and the row loss in ONE launch — the weight staged once per
+ * workgroup (LDS, up to 128 KB; a larger one is read through L2) under a grid-stride walk of the rows — and one small launch for the
+ * fixed-order mean.  `logits` (may be NULL) receives [N, O]; nothing of that size is written otherwise but `saved` [N, O] = p - y (may
+ * be NULL when no backward follows).  The rows may come in any order with their targets in the same order: the mean is symmetric.
+ * O <= 64, D <= 1024 (MANNER_HIP_E_INVALID otherwise); N == 0 is MANNER_HIP_E_INVALID (the mean of nothing).  A target outside [0, O)
+ * — where F.one_hot raises — is never used as an index: it raises MANNER_HIP_STATUS_INDEX in `status` (may be NULL) and its row counts
+ * as loss 0 and gradient 0.
+ * manner_hip_head_ce_backward: from the DEVICE scalar grad_loss [1] and the forward's `saved`, grad_x [N, D], grad_w [O, D] and
+ * grad_b [O]; each may be NULL (a frozen head, rows that need no gradient) and its work is then skipped.  grad_w / grad_b are partial
+ * sums over chunks of ascending rows added in ascending chunk order; `workspace` (_backward_workspace_bytes) is read only for them.
+ * manner_hip_head_l1 / _backward: the O == 1 case of the same row walk with nn.L1Loss: w [D], b [1], target f32 [N] -> loss [1] =
+ * mean |x . w + b - target|; `saved` [N] = sign(residual) with sign(0) = 0 as torch: a row that meets its target exactly sends no
+ * gradient.
+ * manner_hip_senti_div (sentirec_plm_module.py:180-193): the RAGGED scores [T] and candidate sentiment scores [T], the history
+ * sentiment scores [N_hist], hist_off / cand_off int64 [B + 1], c_max = the dense width Cmax -> loss [1] =
+ * (1 / (B c_max)) sum_b sum_c relu(u_b s_bc score_bc), u_b = (the sum of user b's history scores, ascending) / its history length.
+ * Padded slots add 0 and are counted in the divisor.  A user without history has u = 0 / 0: the loss is NaN as in the reference, and so
+ * are the gradients of that user's candidates, and only those.  c_max < 1 or B c_max < T is MANNER_HIP_E_INVALID; a single impression
+ * with more than c_max candidates is seen on the device only and raises MANNER_HIP_STATUS_LENGTHS in `status` (may be NULL).
+ * workspace: 8-byte aligned.  _backward: grad_scores [T] from the DEVICE scalar grad_loss [1]: (g / (B c_max)) u_b s_t where the
+ * product is > 0, exactly 0 where it is <= 0 (a neutral news with s = 0 included).  Every reduction has a fixed order (no
+ * floating-point atomics) and every grid depends on the shape alone. */
+size_t manner_hip_head_workspace_bytes(int64_t N);
+size_t manner_hip_head_backward_workspace_bytes(int64_t N, int32_t D, int32_t O);
+int manner_hip_head_ce(const float* x, const float* w, const float* b, const int64_t* target, int64_t N, int32_t D, int32_t O, float* loss,
+                       float* saved, float* logits, void* workspace, size_t workspace_bytes, int32_t* status, manner_hip_stream_t stream);
+int manner_hip_head_ce_backward(const float* grad_loss, const float* x, const float* w, const float* saved, int64_t N, int32_t D, int32_t O,
+                                float* grad_x, float* grad_w, float* grad_b, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+int manner_hip_head_l1(const float* x, const float* w, const float* b, const float* target, int64_t N, int32_t D, float* loss, float* saved,
+                       void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+int manner_hip_head_l1_backward(const float* grad_loss, const float* x, const float* w, const float* saved, int64_t N, int32_t D, float* grad_x,
+                                float* grad_w, float* grad_b, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+size_t manner_hip_senti_div_workspace_bytes(int64_t B);
+int manner_hip_senti_div(const float* scores, const float* cand_score, const float* hist_score, const int64_t* hist_off, const int64_t* cand_off,
+                         int64_t T, int64_t n_hist, int64_t B, int64_t c_max, float* loss, void* workspace, size_t workspace_bytes, int32_t* status,
+                         manner_hip_stream_t stream);
+int manner_hip_senti_div_backward(const float* grad_loss, const float* scores, const float* cand_score, const float* hist_score,
+                                  const int64_t* hist_off, const int64_t* cand_off, int64_t T, int64_t n_hist, int64_t B, int64_t c_max,
+                                  float* grad_scores, manner_hip_stream_t stream);
+
 /* ---- the CAUM baseline's operators (csrc/caum.hip; f32, forward and backward; additive exports) -------------------------------------
  * manner_hip_axis0_attention_any is manner_hip_axis0_attention at ANY head dim 1 <= E / heads <= 64 (CAUM ships 25 and 5): qkv
  * [L0, B1, 3E] -> out [L0, B1, E], attention along axis 0.  stats [L0 * B1 * heads * 3] (may be NULL in the forward) receives the

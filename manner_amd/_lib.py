@@ -172,6 +172,15 @@ SIGNATURES = {
     "manner_hip_disagreement_loss_workspace_bytes": (_SZ, [_I64]),
     "manner_hip_disagreement_loss": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
     "manner_hip_disagreement_loss_backward": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
+    "manner_hip_head_workspace_bytes": (_SZ, [_I64]),
+    "manner_hip_head_backward_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "manner_hip_head_ce": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
+    "manner_hip_head_ce_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_head_l1": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _SZ, _P]),
+    "manner_hip_head_l1_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_senti_div_workspace_bytes": (_SZ, [_I64]),
+    "manner_hip_senti_div": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P, _P]),
+    "manner_hip_senti_div_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
 }
 
 _lib = None

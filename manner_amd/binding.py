@@ -66,6 +66,12 @@ aggregation and the disagreement loss are built as ``hotpath.miner_forward`` / `
 bookkeeping of ``model_step`` and the Lightning hooks.  A plain ``install()`` binds exactly the first
 table, whatever an earlier call added stays until ``uninstall()``.
 
+``TANRPLMModule`` and ``SentiRecPLMModule`` have nothing to rebind and no baseline name: every leaf class of theirs —
+``PLMTextEncoder``, ``NAMLUserEncoder`` / ``NRMSUserEncoder``, ``DotProduct`` — is in the first table.  Their own lines (the topic /
+sentiment head over every news row, its loss, SentiRec's diversity regulariser) are built as ``hotpath.tanr_train_step`` and
+``hotpath.sentirec_train_step`` (csrc/aspect.hip; ``tanr_forward`` / ``sentirec_forward`` beside them) for a ``forward`` /
+``model_step`` that delegates to them.
+
 Use (no reference source line changes):
 
     python -m manner_amd.run manner/train.py experiment=cr_module_mind_title_scl_lf      # = install() + runpy of the script

@@ -890,6 +890,99 @@ def disagreement_loss(user: Tensor) -> Tensor:
     return loss[0]
 
 
+def _head_operands(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor, target_dtype: torch.dtype, who: str):
+    x = _dev(x, torch.float32, who + ": x").contiguous()
+    weight = _dev(weight, torch.float32, who + ": weight").contiguous()
+    bias = _dev(bias, torch.float32, who + ": bias").contiguous()
+    target = _dev(target, target_dtype, who + ": target").contiguous().reshape(-1)
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or bias.numel() != weight.shape[0] or target.numel() != x.shape[0]:
+        raise ValueError(f"{who}: x [N, D], weight [O, D], bias [O], target [N] expected, got {tuple(x.shape)}, {tuple(weight.shape)}, "
+                         f"{tuple(bias.shape)}, {tuple(target.shape)}")
+    return x, weight, bias, target
+
+
+def _head_ce_forward(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor, saved: Optional[Tensor], logits: Optional[Tensor]) -> Tensor:
+    n, d = x.shape
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.manner_hip_head_workspace_bytes(n))
+        ws = _workspace(need, x.device)
+        _lib.check(lib.manner_hip_head_ce(_ptr(x), _ptr(weight), _ptr(bias), _ptr(target), n, d, weight.shape[0], _ptr(loss), _ptr(saved),
+                                          _ptr(logits), _ptr(ws), need, _ptr(device_status(x.device).word), _stream()))
+    return loss[0]
+
+
+def head_ce_loss(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor, return_logits: bool = False):
+    """TANR's topic head and its loss (reference baselines/tanr_plm_module.py:139-141,172-174) without gradients: x [N, D] news rows,
+    the ``nn.Linear(D, O)``'s weight [O, D] and bias [O], target int64 [N] class indices -> the scalar
+    ``CrossEntropyLoss(x W^T + b, one_hot(target))``, the mean over all N rows; the [N, O] logits reach memory only with
+    ``return_logits`` (-> (loss, logits)).  O <= 64, D <= 1024; a class outside [0, O), where ``F.one_hot`` raises, raises at
+    ``check_status``."""
+    x, weight, bias, target = _head_operands(x, weight, bias, target, torch.int64, "head_ce_loss")
+    logits = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.float32, device=x.device) if return_logits else None
+    loss = _head_ce_forward(x, weight, bias, target, None, logits)
+    return (loss, logits) if return_logits else loss
+
+
+def _head_l1_forward(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor, saved: Optional[Tensor]) -> Tensor:
+    n, d = x.shape
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.manner_hip_head_workspace_bytes(n))
+        ws = _workspace(need, x.device)
+        _lib.check(lib.manner_hip_head_l1(_ptr(x), _ptr(weight), _ptr(bias), _ptr(target), n, d, _ptr(loss), _ptr(saved), _ptr(ws), need, _stream()))
+    return loss[0]
+
+
+def _head_l1_operands(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor):
+    x, weight, bias, target = _head_operands(x, weight, bias, target, torch.float32, "head_l1_loss")
+    if weight.shape[0] != 1:
+        raise ValueError(f"head_l1_loss: weight [1, D] expected (nn.Linear(D, 1)), got {tuple(weight.shape)}")
+    return x, weight, bias, target
+
+
+def head_l1_loss(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor) -> Tensor:
+    """SentiRec's sentiment head and its loss (reference baselines/sentirec_plm_module.py:141-143,174-177) without gradients: x [N, D],
+    the ``nn.Linear(D, 1)``'s weight [1, D] and bias [1], target f32 [N] -> the scalar ``L1Loss((x w + b).flatten(), target)``.
+    D <= 1024."""
+    return _head_l1_forward(*_head_l1_operands(x, weight, bias, target), None)
+
+
+def _senti_div_operands(scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_off: Tensor, cand_off: Tensor, c_max: int):
+    scores = _dev(scores, torch.float32, "senti_div_loss: scores").contiguous().reshape(-1)
+    cand_score = _dev(cand_score, torch.float32, "x_cand.sentiment_score").contiguous().reshape(-1)
+    hist_score = _dev(hist_score, torch.float32, "x_hist.sentiment_score").contiguous().reshape(-1)
+    hist_off = _dev(hist_off, torch.int64, "hist_off").contiguous()
+    cand_off = _dev(cand_off, torch.int64, "cand_off").contiguous()
+    if cand_score.numel() != scores.numel() or hist_off.numel() != cand_off.numel() or cand_off.numel() < 2:
+        raise ValueError("senti_div_loss: ragged scores [T], candidate sentiment scores [T], hist_off / cand_off [B + 1] expected")
+    return scores, cand_score, hist_score, hist_off, cand_off, int(c_max)
+
+
+def _senti_div_forward(scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_off: Tensor, cand_off: Tensor, c_max: int) -> Tensor:
+    b = cand_off.numel() - 1
+    loss = torch.empty(1, dtype=torch.float32, device=scores.device)
+    lib = _lib.load()
+    with torch.cuda.device(scores.device):
+        need = int(lib.manner_hip_senti_div_workspace_bytes(b))
+        ws = _workspace(need, scores.device)
+        _lib.check(lib.manner_hip_senti_div(_ptr(scores), _ptr(cand_score), _ptr(hist_score), _ptr(hist_off), _ptr(cand_off), scores.numel(),
+                                            hist_score.numel(), b, c_max, _ptr(loss), _ptr(ws), need, _ptr(device_status(scores.device).word),
+                                            _stream()))
+    return loss[0]
+
+
+def senti_div_loss(scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_off: Tensor, cand_off: Tensor, c_max: int) -> Tensor:
+    """SentiRec's sentiment diversity regulariser (reference baselines/sentirec_plm_module.py:180-193) without gradients, on the RAGGED
+    scores [sum c_i]: ``relu(u[b] * s_cand[b, c] * scores[b, c]).mean()`` over the dense [B, c_max] block, u[b] = the mean sentiment
+    score of user b's history.  Padded slots add 0 and count in the divisor B * c_max; a user without history gives NaN, as the
+    reference's 0 / 0 does.  ``c_max`` below the largest candidate count is refused — at ``check_status`` where only the device can
+    know."""
+    return _senti_div_forward(*_senti_div_operands(scores, cand_score, hist_score, hist_off, cand_off, c_max))
+
+
 def axis0_attention_any(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
     """The attention core of ``mha_axis0_any`` on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]; ``stats`` f32 [L0 * B1 * heads * 3]
     receives the softmax statistics the backward reads."""

@@ -7,6 +7,8 @@
   — mode R of SURVEY.md §8d: every history and candidate occurrence is encoded.
 * ``caum_forward`` / ``caum_train_step`` and ``miner_forward`` / ``miner_train_step`` do the same for ``CAUMPLMModule`` and
   ``MINERModule`` (reference manner/models/baselines/): the module's own lines between the mirrored leaf classes.
+* ``tanr_forward`` / ``tanr_train_step`` and ``sentirec_forward`` / ``sentirec_train_step`` are ``TANRPLMModule`` and
+  ``SentiRecPLMModule``: the auxiliary head over every news row, its loss and SentiRec's diversity regulariser (csrc/aspect.hip).
 * ``encode_table`` / ``score_impressions`` are the table architecture (mode T): each unique news is
   encoded once per module into ``[N_news, D]``, impressions are scored by index.  Valid for
   ``use_entities=False`` only.
@@ -257,6 +259,104 @@ def miner_train_step(news_encoder, user_encoder, batch: Dict, *, score_type: str
         c_max = _width(batch, "cand_max", cand_off)
     ce, _ = train.model_step_loss(ragged, batch["labels"].to(torch.float32), cand_off, supcon=False, c_max=c_max)
     return ce + train.disagreement_loss(user_vector), ragged.detach(), cand_off
+
+
+def _encode_joined(news_encoder, th: Dict, tc: Dict):
+    """Both token sets through ONE call of a PLMTextEncoder, as ``encode_hist_and_cand`` -> (rows [N_hist + N_cand, D] as the encoder
+    left them, history first; N_hist)."""
+    cfg = getattr(getattr(news_encoder, "plm_model", None), "cfg", None)
+    return news_encoder(_cat_tokens(th, tc, cfg.pad_id if cfg is not None else 0)), th["input_ids"].shape[0]
+
+
+def _aspect_scores(hist_vec: Tensor, cand_vec: Tensor, user_encoder, batch: Dict, nb: int):
+    """The lines TANRPLMModule.forward and SentiRecPLMModule.forward share below the encoder calls (tanr_plm_module.py:125-136): both
+    sides to dense, the user encoder (NAMLUserEncoder / NRMSUserEncoder of this package), DotProduct -> (scores [B, Cmax], hist_off,
+    cand_off, Cmax); a zero-padded candidate row scores exactly 0."""
+    hist_off = segment_offsets(batch["batch_hist"], nb)
+    cand_off = segment_offsets(batch["batch_cand"], nb)
+    s, c_max = _width(batch, "hist_max", hist_off), _width(batch, "cand_max", cand_off)
+    graph = torch.is_grad_enabled()
+    dense_of = train.to_dense if graph and (hist_vec.requires_grad or cand_vec.requires_grad) else hip.to_dense
+    user = user_encoder(dense_of(hist_vec, hist_off, s))
+    cand_dense = dense_of(cand_vec, cand_off, c_max)
+    dot = train.dot if graph and (user.requires_grad or cand_dense.requires_grad) else hip.dot
+    return dot(user.unsqueeze(1), cand_dense.permute(0, 2, 1)), hist_off, cand_off, c_max
+
+
+def _aspect_forward(news_encoder, user_encoder, predictor, batch: Dict, dense: bool):
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    hist_vec = news_encoder(batch["x_hist"]["text"])
+    cand_vec = news_encoder(batch["x_cand"]["text"])
+    scores, _, cand_off, c_max = _aspect_scores(hist_vec, cand_vec, user_encoder, batch, nb)
+    graph = torch.is_grad_enabled() and (cand_vec.requires_grad or predictor.weight.requires_grad)
+    lin = train.linear if graph else hip.linear
+    w, b = (predictor.weight, predictor.bias) if graph else (predictor.weight.detach(), predictor.bias.detach())
+    head = torch.cat((lin(cand_vec, w, b), lin(hist_vec, w, b)), dim=0)      # the reference's order; O columns wide, not D
+    hip.status_arm(cand_vec.device)
+    if not dense:
+        scores = scores.reshape(-1).index_select(0, train.dense_slots(cand_off, int(batch["batch_cand"].numel()), c_max))
+    return scores, head
+
+
+def tanr_forward(news_encoder, user_encoder, topic_predictor, batch: Dict, dense: bool = True):
+    """TANRPLMModule.forward (reference baselines/tanr_plm_module.py:122-143) -> (scores [B, Cmax], topic_scores [N, num_topics]): the
+    two news-encoder calls on ``batch["x_hist"]["text"]`` / ``batch["x_cand"]["text"]``, both sides to dense, ``user_encoder`` (the
+    NAMLUserEncoder of this package), DotProduct, and ``topic_predictor`` (the module's own nn.Linear) over the candidate rows, then
+    the history rows — this path materialises the logits; ``tanr_train_step`` does not.  Padded score slots are exactly 0;
+    ``dense=False`` returns the ragged [sum c_i] scores.  No host synchronisation when the batch carries ``hist_max`` / ``cand_max``."""
+    return _aspect_forward(news_encoder, user_encoder, topic_predictor, batch, dense)
+
+
+def sentirec_forward(news_encoder, user_encoder, sentiment_predictor, batch: Dict, dense: bool = True):
+    """SentiRecPLMModule.forward (reference baselines/sentirec_plm_module.py:124-145) -> (scores [B, Cmax], senti_scores [N, 1]):
+    ``tanr_forward`` with the NRMSUserEncoder of this package and the module's ``nn.Linear(D, 1)``."""
+    return _aspect_forward(news_encoder, user_encoder, sentiment_predictor, batch, dense)
+
+
+def _aspect_step(news_encoder, user_encoder, batch: Dict):
+    """forward for a step: ONE encoder call -> (rows [N_hist + N_cand, D] history first, ragged scores, hist_off, cand_off, Cmax, CE)"""
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    rows, n_hist = _encode_joined(news_encoder, batch["x_hist"]["text"], batch["x_cand"]["text"])
+    dense, hist_off, cand_off, c_max = _aspect_scores(rows[:n_hist], rows[n_hist:], user_encoder, batch, nb)
+    ragged = dense.reshape(-1).index_select(0, train.dense_slots(cand_off, int(batch["batch_cand"].numel()), c_max))
+    ce, _ = train.model_step_loss(ragged, batch["labels"].to(torch.float32), cand_off, supcon=False, c_max=c_max)
+    return rows, ragged, hist_off, cand_off, c_max, ce
+
+
+def _head_params(predictor):
+    return (predictor.weight, predictor.bias) if torch.is_grad_enabled() else (predictor.weight.detach(), predictor.bias.detach())
+
+
+def tanr_train_step(news_encoder, user_encoder, topic_predictor, batch: Dict, topic_pred_loss_coef: float):
+    """The loss lines of TANRPLMModule.model_step (reference baselines/tanr_plm_module.py:157-177): ``forward`` with both news sets
+    through ONE encoder call, ``nn.CrossEntropyLoss(scores [B, Cmax], y_true)`` from the ragged scores, plus ``topic_pred_loss_coef``
+    times the topic head's cross-entropy over every news row — ``train.head_ce_loss`` on the encoder's output as it lies (history
+    rows, then candidate rows, the categories in the same order: the mean does not depend on the order), no ``torch.cat`` of the rows,
+    no one-hot matrix, no [N, num_topics] logits.  Under ``torch.no_grad()`` (val/loss, test/loss) the same kernels run without
+    saving anything.  Returns (loss, ragged scores [sum c_i] detached, cand_off); the metrics bookkeeping of ``model_step`` is the
+    caller's.  No host synchronisation when the batch carries ``hist_max`` / ``cand_max``."""
+    rows, ragged, _, cand_off, _, ce = _aspect_step(news_encoder, user_encoder, batch)
+    topics = torch.cat((batch["x_hist"]["category"].reshape(-1), batch["x_cand"]["category"].reshape(-1))).to(torch.int64)
+    head = (train.head_ce_loss if torch.is_grad_enabled() else hip.head_ce_loss)(rows, *_head_params(topic_predictor), topics)
+    hip.status_arm(rows.device)
+    return ce + float(topic_pred_loss_coef) * head, ragged.detach(), cand_off
+
+
+def sentirec_train_step(news_encoder, user_encoder, sentiment_predictor, batch: Dict, senti_pred_loss_coef: float, senti_div_loss_coef: float):
+    """The loss lines of SentiRecPLMModule.model_step (reference baselines/sentirec_plm_module.py:159-193): as ``tanr_train_step`` with
+    ``nn.L1Loss`` of the sentiment head over every news row (``train.head_l1_loss``) times ``senti_pred_loss_coef``, plus
+    ``senti_div_loss_coef`` times the diversity regulariser ``relu(u * s_cand * scores).mean()`` over the dense [B, Cmax] block —
+    ``train.senti_div_loss`` on the ragged scores, the user's mean history sentiment formed on the device: no dense blocks, no
+    per-impression host loop, no host read.  Returns (loss, ragged scores [sum c_i] detached, cand_off)."""
+    rows, ragged, hist_off, cand_off, c_max, ce = _aspect_step(news_encoder, user_encoder, batch)
+    hs, cs = batch["x_hist"]["sentiment_score"].reshape(-1).to(torch.float32), batch["x_cand"]["sentiment_score"].reshape(-1).to(torch.float32)
+    graph = torch.is_grad_enabled()
+    head = (train.head_l1_loss if graph else hip.head_l1_loss)(rows, *_head_params(sentiment_predictor), torch.cat((hs, cs)))
+    div = (train.senti_div_loss if graph else hip.senti_div_loss)(ragged, cs, hs, hist_off, cand_off, c_max)
+    hip.status_arm(rows.device)
+    return ce + float(senti_pred_loss_coef) * head + float(senti_div_loss_coef) * div, ragged.detach(), cand_off
 
 
 def a_train_step(news_encoder, batch: Dict, temperature: float = 0.1):

@@ -653,6 +653,87 @@ def disagreement_loss(user: Tensor) -> Tensor:
     return _Disagreement.apply(hip._disagreement_operand(user))
 
 
+def _head_backward(entry, ctx, g: Tensor, x: Tensor, weight: Tensor, saved: Tensor, dims):
+    """The shared backward of the two row heads: the device-scalar upstream gradient goes to the library as it is; an input that needs
+    no gradient (a frozen head, detached rows) passes NULL and its kernel is skipped."""
+    need_x, need_w, need_b = ctx.needs_input_grad[:3]
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty_like(weight) if need_w else None
+    db = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device) if need_b else None
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        g = _f32(g, "grad").reshape(1)                           # stays on the device: nothing is read back
+        need = int(lib.manner_hip_head_backward_workspace_bytes(x.shape[0], x.shape[1], weight.shape[0])) if (need_w or need_b) else 0
+        ws = hip._workspace(need, x.device) if need else None
+        _lib.check(entry(lib)(hip._ptr(g), hip._ptr(x), hip._ptr(weight), hip._ptr(saved), *dims, hip._ptr(dx), hip._ptr(dw), hip._ptr(db),
+                              hip._ptr(ws), need, hip._stream()))
+    return dx, dw, db, None
+
+
+class _HeadCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, bias: Tensor, target: Tensor):
+        saved = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.float32, device=x.device)      # p - y
+        loss = hip._head_ce_forward(x, weight, bias, target, saved, None)
+        ctx.save_for_backward(x, weight, saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, weight, saved = ctx.saved_tensors
+        return _head_backward(lambda lib: lib.manner_hip_head_ce_backward, ctx, g, x, weight, saved, (x.shape[0], x.shape[1], weight.shape[0]))
+
+
+def head_ce_loss(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor) -> Tensor:
+    """``hip.head_ce_loss`` with autograd into the rows, the weight and the bias: ``CrossEntropyLoss(Linear(x), one_hot(target))`` in one
+    fused forward, gradients from the saved p - y with fixed-order sums over the rows."""
+    return _HeadCE.apply(*hip._head_operands(x, weight, bias, target, torch.int64, "head_ce_loss"))
+
+
+class _HeadL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, bias: Tensor, target: Tensor):
+        saved = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)                           # sign(residual)
+        loss = hip._head_l1_forward(x, weight, bias, target, saved)
+        ctx.save_for_backward(x, weight, saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, weight, saved = ctx.saved_tensors
+        return _head_backward(lambda lib: lib.manner_hip_head_l1_backward, ctx, g, x, weight, saved, (x.shape[0], x.shape[1]))
+
+
+def head_l1_loss(x: Tensor, weight: Tensor, bias: Tensor, target: Tensor) -> Tensor:
+    """``hip.head_l1_loss`` with autograd: ``L1Loss(Linear(D, 1)(x).flatten(), target)``; a residual of exactly 0 sends no gradient
+    (sign(0) = 0, as torch)."""
+    return _HeadL1.apply(*hip._head_l1_operands(x, weight, bias, target))
+
+
+class _SentiDiv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_off: Tensor, cand_off: Tensor, c_max: int):
+        ctx.save_for_backward(scores, cand_score, hist_score, hist_off, cand_off)
+        ctx.c_max = c_max
+        return hip._senti_div_forward(scores, cand_score, hist_score, hist_off, cand_off, c_max)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        scores, cand_score, hist_score, hist_off, cand_off = ctx.saved_tensors
+        ds = torch.zeros_like(scores)
+        with torch.cuda.device(scores.device):
+            g = _f32(g, "grad").reshape(1)                       # stays on the device: nothing is read back
+            _lib.check(_lib.load().manner_hip_senti_div_backward(hip._ptr(g), hip._ptr(scores), hip._ptr(cand_score), hip._ptr(hist_score),
+                                                                 hip._ptr(hist_off), hip._ptr(cand_off), scores.numel(), hist_score.numel(),
+                                                                 cand_off.numel() - 1, ctx.c_max, hip._ptr(ds), hip._stream()))
+        return ds, None, None, None, None, None
+
+
+def senti_div_loss(scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_off: Tensor, cand_off: Tensor, c_max: int) -> Tensor:
+    """``hip.senti_div_loss`` with autograd into the ragged scores: the gradient is 0 where the product u s score is <= 0."""
+    return _SentiDiv.apply(*hip._senti_div_operands(scores, cand_score, hist_score, hist_off, cand_off, c_max))
+
+
 class _Axis0Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv: Tensor, heads: int):
