@@ -739,6 +739,61 @@ int manner_hip_senti_div_backward(const float* grad_loss, const float* scores, c
                                   const int64_t* hist_off, const int64_t* cand_off, int64_t T, int64_t n_hist, int64_t B, int64_t c_max,
                                   float* grad_scores, manner_hip_stream_t stream);
 
+/* ---- SentiDebias-PLM's generator and discriminator lines (csrc/debias.hip; f32, forward and backward; additive exports) --------------
+ * What baselines/senti_debias_plm_module.py:94-148,163-167,275-280 compute beside the leaf classes.  The sentiment encoder has only
+ * C = num_sent_classes distinct outputs, the class table `table` [C, D] = tanh(linear(embedding.weight)) that the caller forms with
+ * manner_hip_linear_tanh on C rows; `cls` int64 holds a row's class and the [N, D] sentiment rows are never written.  A class outside
+ * [0, C) is never used as an index: it raises MANNER_HIP_STATUS_INDEX in `status` (may be NULL) and its row counts as 0, gradient 0.
+ * Every reduction has a fixed order (no floating-point atomics), every grid depends on the shape alone; NULL gradient pointers skip
+ * their kernels.  N < 2^31, C <= 64.
+ * manner_hip_orth_loss: rows [N, D] (the first n_hist are the history's), user_free / user_aware [B, D] -> loss [1] =
+ * |mean_{i < n_hist} cos(rows_i, table[cls_i])| + |mean_{i >= n_hist} cos(...)| + mean_b |cos(user_free_b, user_aware_b)| with
+ * cos(a, b) = a . b / (1e-8 + |a| |b|); `means` [2] receives the two signed means (the backward's signs).  An empty segment is NaN.
+ * D <= 1024 (a row in registers).  _backward: from the DEVICE scalar grad_loss [1], grad_rows [N, D], grad_user_free / _aware [B, D] and
+ * grad_table [C, D], per-class sums over chunks of ascending rows added in ascending chunk order; a zero vector receives torch's zero
+ * gradient through its norm.
+ * manner_hip_class_dense: off int64 [B + 1] -> out [B, width, D] = to_dense_batch of table[cls], zero padding; B width >= N
+ * (MANNER_HIP_E_INVALID otherwise; a single user with more than `width` rows raises MANNER_HIP_STATUS_LENGTHS).  _backward: grad_out
+ * [B, width, D] -> grad_table by the same binned sums.
+ * manner_hip_class_scores: user [B, D] -> out [N] = user_b . table[cls_t] for the ragged candidates t of user b (off [B + 1]), read
+ * from the [B, C] products.  _backward: grad_user [B, D], grad_table [C, D] from the per-(user, class) sums of grad_out.
+ * manner_hip_adv_loss: Discriminator.forward and adversarial_loss on both row sets: loss [1] = mean_{i < n_hist} CE_i +
+ * mean_{i >= n_hist} CE_i, CE_i = -log softmax(w2 tanh(w1 rows_i + b1) + b2)[(cls_i - 1) mod O] (the module writes
+ * y_true[i, t - 1] = 1: class 0 lands on the last column); cls is validated against [0, O).  w1 [H, D], w2 [O, H].  Layer 1 runs on
+ * the f32 matrix cores, layer 2 with the softmax as a row walk under w2 staged in LDS (up to 128 KB, read through L2 past it).
+ * `hidden` [N, H] receives the activation; `saved` [N, O] (may be NULL when no backward follows) (p - y) / rows of the segment.
+ * O <= 64, H <= 1024 (a hidden row in registers), D <= 1024 (the rows are orth_loss's).  _backward: grad_rows through the matrix cores,
+ * grad_w1 through manner_hip_wgrad_rows_f32, grad_b1 / grad_w2 / grad_b2 as chunked fixed-order sums; any subset may be NULL and the
+ * others keep their bits. */
+size_t manner_hip_orth_loss_workspace_bytes(int64_t N, int64_t B);
+size_t manner_hip_orth_loss_backward_workspace_bytes(int64_t N, int32_t D, int32_t C);
+int manner_hip_orth_loss(const float* rows, int64_t N, int64_t n_hist, const float* table, const int64_t* cls, const float* user_free,
+                         const float* user_aware, int64_t B, int32_t D, int32_t C, float* loss, float* means, void* workspace, size_t workspace_bytes,
+                         int32_t* status, manner_hip_stream_t stream);
+int manner_hip_orth_loss_backward(const float* grad_loss, const float* means, const float* rows, int64_t N, int64_t n_hist, const float* table,
+                                  const int64_t* cls, const float* user_free, const float* user_aware, int64_t B, int32_t D, int32_t C,
+                                  float* grad_rows, float* grad_table, float* grad_user_free, float* grad_user_aware, void* workspace,
+                                  size_t workspace_bytes, manner_hip_stream_t stream);
+size_t manner_hip_class_dense_backward_workspace_bytes(int64_t B, int64_t width, int32_t D, int32_t C);
+int manner_hip_class_dense(const float* table, const int64_t* cls, const int64_t* off, int64_t N, int64_t B, int64_t width, int32_t D, int32_t C,
+                           float* out, int32_t* status, manner_hip_stream_t stream);
+int manner_hip_class_dense_backward(const float* grad_out, const int64_t* cls, const int64_t* off, int64_t N, int64_t B, int64_t width, int32_t D,
+                                    int32_t C, float* grad_table, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+size_t manner_hip_class_scores_workspace_bytes(int64_t B, int32_t C);
+int manner_hip_class_scores(const float* user, const float* table, const int64_t* cls, const int64_t* off, int64_t N, int64_t B, int32_t D, int32_t C,
+                            float* out, void* workspace, size_t workspace_bytes, int32_t* status, manner_hip_stream_t stream);
+int manner_hip_class_scores_backward(const float* grad_out, const float* user, const float* table, const int64_t* cls, const int64_t* off, int64_t N,
+                                     int64_t B, int32_t D, int32_t C, float* grad_user, float* grad_table, void* workspace, size_t workspace_bytes,
+                                     manner_hip_stream_t stream);
+size_t manner_hip_adv_loss_workspace_bytes(int64_t N);
+size_t manner_hip_adv_loss_backward_workspace_bytes(int64_t N, int32_t D, int32_t H, int32_t O);
+int manner_hip_adv_loss(const float* rows, int64_t N, int64_t n_hist, const float* w1, const float* b1, const float* w2, const float* b2,
+                        const int64_t* cls, int32_t D, int32_t H, int32_t O, float* loss, float* hidden, float* saved, void* workspace,
+                        size_t workspace_bytes, int32_t* status, manner_hip_stream_t stream);
+int manner_hip_adv_loss_backward(const float* grad_loss, const float* rows, int64_t N, const float* w1, const float* w2, const float* hidden,
+                                 const float* saved, int32_t D, int32_t H, int32_t O, float* grad_rows, float* grad_w1, float* grad_b1, float* grad_w2,
+                                 float* grad_b2, void* workspace, size_t workspace_bytes, manner_hip_stream_t stream);
+
 /* ---- the CAUM baseline's operators (csrc/caum.hip; f32, forward and backward; additive exports) -------------------------------------
  * manner_hip_axis0_attention_any is manner_hip_axis0_attention at ANY head dim 1 <= E / heads <= 64 (CAUM ships 25 and 5): qkv
  * [L0, B1, 3E] -> out [L0, B1, E], attention along axis 0.  stats [L0 * B1 * heads * 3] (may be NULL in the forward) receives the

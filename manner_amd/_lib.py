@@ -181,6 +181,20 @@ SIGNATURES = {
     "manner_hip_senti_div_workspace_bytes": (_SZ, [_I64]),
     "manner_hip_senti_div": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P, _P]),
     "manner_hip_senti_div_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "manner_hip_orth_loss_workspace_bytes": (_SZ, [_I64, _I64]),
+    "manner_hip_orth_loss_backward_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "manner_hip_orth_loss": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _SZ, _P, _P]),
+    "manner_hip_orth_loss_backward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_class_dense_backward_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
+    "manner_hip_class_dense": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    "manner_hip_class_dense_backward": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _SZ, _P]),
+    "manner_hip_class_scores_workspace_bytes": (_SZ, [_I64, _I32]),
+    "manner_hip_class_scores": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _SZ, _P, _P]),
+    "manner_hip_class_scores_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    "manner_hip_adv_loss_workspace_bytes": (_SZ, [_I64]),
+    "manner_hip_adv_loss_backward_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "manner_hip_adv_loss": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
+    "manner_hip_adv_loss_backward": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

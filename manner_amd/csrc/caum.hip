@@ -1233,6 +1233,15 @@ void plan_work_all(Bump& b, WorkAll& a, const Dims& m) {
 }
 
 }  // namespace
+
+// launch_wlin and launch_mdx for the other translation units (declared in common.h): flat rows, no per-(user, column) terms
+int wlin_f32(bool tanh_act, const float* x, int ldx, const float* W, int ldw, const float* bias, int64_t R, int K, int O, float* y, int ldy,
+             hipStream_t s) {
+  return launch_wlin(tanh_act, x, ldx, W, ldw, bias, nullptr, nullptr, RowMap{1, 1, 1, 0}, R, K, O, y, ldy, s);
+}
+int wlin_dx_f32(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, float* dx, float* wt, hipStream_t s) {
+  return launch_mdx(dy, ldy, W, ldw, R, K, O, nullptr, nullptr, dx, wt, s);
+}
 }  // namespace manner
 
 using namespace manner;

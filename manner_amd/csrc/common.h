@@ -185,4 +185,12 @@ int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, in
 int attention_cls(DType dt, const void* qcls, const void* kv, void* ctx_cls, const int32_t* cu, int64_t n_news,
                   int heads, int H, hipStream_t stream);
 
+// ------------------------------------------------------------------ f32 matrix-core linear (caum.hip)
+// y [R, O] = act(bias + x W^T) on wlin_kernel: x rows ldx apart, W [O, K] rows ldw apart, y rows ldy apart, bias may be NULL; R >= 1.
+// The 32 x 32 tile below 1024 rows, 128 x 64 from there on; an output is one k-ascending fmaf chain in either.
+int wlin_f32(bool tanh_act, const float* x, int ldx, const float* W, int ldw, const float* bias, int64_t R, int K, int O, float* y, int ldy,
+             hipStream_t stream);
+// dx [R, K] = dy [R, O] W [O, K] on the same kernel: W (rows ldw apart) is transposed into wt [K, O] first; R >= 1
+int wlin_dx_f32(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, float* dx, float* wt, hipStream_t stream);
+
 }  // namespace manner

@@ -983,6 +983,137 @@ def senti_div_loss(scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_
     return _senti_div_forward(*_senti_div_operands(scores, cand_score, hist_score, hist_off, cand_off, c_max))
 
 
+# ---- SentiDebias-PLM's generator and discriminator lines (csrc/debias.hip)
+def _class_operands(table: Tensor, cls: Tensor, who: str):
+    table = _dev(table, torch.float32, who + ": class table").contiguous()
+    cls = _dev(cls, torch.int64, who + ": classes").contiguous().reshape(-1)
+    if table.dim() != 2:
+        raise ValueError(f"{who}: class table [C, D] expected, got {tuple(table.shape)}")
+    return table, cls
+
+
+def _orth_operands(rows: Tensor, n_hist: int, table: Tensor, cls: Tensor, user_free: Tensor, user_aware: Tensor):
+    table, cls = _class_operands(table, cls, "orth_loss")
+    rows = _dev(rows, torch.float32, "orth_loss: rows").contiguous()
+    user_free = _dev(user_free, torch.float32, "orth_loss: user_free").contiguous()
+    user_aware = _dev(user_aware, torch.float32, "orth_loss: user_aware").contiguous()
+    d = table.shape[1]
+    if rows.dim() != 2 or rows.shape[1] != d or cls.numel() != rows.shape[0] or user_free.dim() != 2 or user_free.shape[1] != d \
+            or user_aware.shape != user_free.shape or not 0 <= int(n_hist) <= rows.shape[0]:
+        raise ValueError(f"orth_loss: rows [N, D], 0 <= n_hist <= N, table [C, D], classes [N], user_free / user_aware [B, D] expected, got "
+                         f"{tuple(rows.shape)}, {n_hist}, {tuple(table.shape)}, {tuple(cls.shape)}, {tuple(user_free.shape)}, {tuple(user_aware.shape)}")
+    return rows, int(n_hist), table, cls, user_free, user_aware
+
+
+def _orth_forward(rows: Tensor, n_hist: int, table: Tensor, cls: Tensor, user_free: Tensor, user_aware: Tensor, means: Optional[Tensor]) -> Tensor:
+    n, b = rows.shape[0], user_free.shape[0]
+    loss = torch.empty(1, dtype=torch.float32, device=rows.device)
+    lib = _lib.load()
+    with torch.cuda.device(rows.device):
+        need = int(lib.manner_hip_orth_loss_workspace_bytes(n, b))
+        ws = _workspace(need, rows.device)
+        _lib.check(lib.manner_hip_orth_loss(_ptr(rows), n, n_hist, _ptr(table), _ptr(cls), _ptr(user_free), _ptr(user_aware), b, table.shape[1],
+                                            table.shape[0], _ptr(loss), _ptr(means), _ptr(ws), need, _ptr(device_status(rows.device).word), _stream()))
+    return loss[0]
+
+
+def orth_loss(rows: Tensor, n_hist: int, table: Tensor, cls: Tensor, user_free: Tensor, user_aware: Tensor) -> Tensor:
+    """SentiDebias's three orthogonality terms (reference baselines/senti_debias_plm_module.py:109-135) without gradients: rows [N, D]
+    news vectors, the first ``n_hist`` the history's, ``table`` [C, D] the sentiment encoder's C distinct outputs, ``cls`` int64 [N] each
+    row's sentiment class, user_free / user_aware [B, D] -> the scalar ``|mean_hist cos| + |mean_cand cos| + mean_b |cos_b|`` with
+    ``cos(a, b) = a . b / (1e-8 + |a| |b|)``.  The [N, D] sentiment rows are never formed.  An empty segment gives NaN, as ``torch.mean``
+    of nothing.  C <= 64, D <= 1024; a class outside [0, C) raises at ``check_status``."""
+    return _orth_forward(*_orth_operands(rows, n_hist, table, cls, user_free, user_aware), None)
+
+
+def _class_dense_operands(table: Tensor, cls: Tensor, off: Tensor, width: int):
+    table, cls = _class_operands(table, cls, "class_dense")
+    off = _dev(off, torch.int64, "class_dense: offsets").contiguous()
+    if off.dim() != 1 or off.numel() < 1:
+        raise ValueError("class_dense: offsets [B + 1] expected")
+    return table, cls, off, int(width)
+
+
+def _class_dense_forward(table: Tensor, cls: Tensor, off: Tensor, width: int) -> Tensor:
+    b = off.numel() - 1
+    out = torch.empty((b, width, table.shape[1]), dtype=torch.float32, device=table.device)
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().manner_hip_class_dense(_ptr(table), _ptr(cls), _ptr(off), cls.numel(), b, width, table.shape[1], table.shape[0],
+                                                      _ptr(out), _ptr(device_status(table.device).word), _stream()))
+    return out
+
+
+def class_dense(table: Tensor, cls: Tensor, off: Tensor, width: int) -> Tensor:
+    """``to_dense_batch`` of the sentiment rows ``table[cls]`` (reference baselines/senti_debias_plm_module.py:95-100) without forming
+    them: table [C, D], cls int64 [N], off int64 [B + 1] -> [B, width, D], padded slots exactly 0.  ``B * width < N`` is refused; a
+    single user with more than ``width`` rows raises at ``check_status``.  C <= 64."""
+    return _class_dense_forward(*_class_dense_operands(table, cls, off, width))
+
+
+def _class_scores_operands(user: Tensor, table: Tensor, cls: Tensor, off: Tensor):
+    table, cls = _class_operands(table, cls, "class_scores")
+    user = _dev(user, torch.float32, "class_scores: user").contiguous()
+    off = _dev(off, torch.int64, "class_scores: offsets").contiguous()
+    if user.dim() != 2 or user.shape[1] != table.shape[1] or off.numel() != user.shape[0] + 1:
+        raise ValueError(f"class_scores: user [B, D], table [C, D], offsets [B + 1] expected, got {tuple(user.shape)}, {tuple(table.shape)}, "
+                         f"{tuple(off.shape)}")
+    return user, table, cls, off
+
+
+def _class_scores_forward(user: Tensor, table: Tensor, cls: Tensor, off: Tensor) -> Tensor:
+    b, c = user.shape[0], table.shape[0]
+    out = torch.empty(cls.numel(), dtype=torch.float32, device=user.device)
+    lib = _lib.load()
+    with torch.cuda.device(user.device):
+        need = int(lib.manner_hip_class_scores_workspace_bytes(b, c))
+        ws = _workspace(need, user.device)
+        _lib.check(lib.manner_hip_class_scores(_ptr(user), _ptr(table), _ptr(cls), _ptr(off), cls.numel(), b, table.shape[1], c, _ptr(out), _ptr(ws),
+                                               need, _ptr(device_status(user.device).word), _stream()))
+    return out
+
+
+def class_scores(user: Tensor, table: Tensor, cls: Tensor, off: Tensor) -> Tensor:
+    """SentiDebias's bias-aware scores (reference baselines/senti_debias_plm_module.py:142-145) on the ragged candidates: user [B, D] the
+    bias-aware user vectors, table [C, D], cls int64 [sum c_i] the candidates' sentiment classes, off int64 [B + 1] -> [sum c_i],
+    ``user_b . table[cls_t]`` read from the [B, C] products — no dense [B, Cmax, D] block, no permute, no bmm.  C <= 64."""
+    return _class_scores_forward(*_class_scores_operands(user, table, cls, off))
+
+
+def _adv_operands(rows: Tensor, n_hist: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, cls: Tensor):
+    rows = _dev(rows, torch.float32, "adv_loss: rows").contiguous()
+    w1, b1 = _dev(w1, torch.float32, "adv_loss: linear1.weight").contiguous(), _dev(b1, torch.float32, "adv_loss: linear1.bias").contiguous()
+    w2, b2 = _dev(w2, torch.float32, "adv_loss: linear2.weight").contiguous(), _dev(b2, torch.float32, "adv_loss: linear2.bias").contiguous()
+    cls = _dev(cls, torch.int64, "adv_loss: classes").contiguous().reshape(-1)
+    if rows.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or w1.shape[1] != rows.shape[1] or w2.shape[1] != w1.shape[0] or b1.numel() != w1.shape[0] \
+            or b2.numel() != w2.shape[0] or cls.numel() != rows.shape[0] or not 0 <= int(n_hist) <= rows.shape[0]:
+        raise ValueError(f"adv_loss: rows [N, D], 0 <= n_hist <= N, linear1 [H, D] / [H], linear2 [O, H] / [O], classes [N] expected, got "
+                         f"{tuple(rows.shape)}, {n_hist}, {tuple(w1.shape)}, {tuple(b1.shape)}, {tuple(w2.shape)}, {tuple(b2.shape)}, {tuple(cls.shape)}")
+    return rows, int(n_hist), w1, b1, w2, b2, cls
+
+
+def _adv_forward(rows: Tensor, n_hist: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, cls: Tensor, hidden: Tensor, saved: Optional[Tensor]) -> Tensor:
+    n, d = rows.shape
+    loss = torch.empty(1, dtype=torch.float32, device=rows.device)
+    lib = _lib.load()
+    with torch.cuda.device(rows.device):
+        need = int(lib.manner_hip_adv_loss_workspace_bytes(n))
+        ws = _workspace(need, rows.device)
+        _lib.check(lib.manner_hip_adv_loss(_ptr(rows), n, n_hist, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(cls), d, w1.shape[0], w2.shape[0],
+                                           _ptr(loss), _ptr(hidden), _ptr(saved), _ptr(ws), need, _ptr(device_status(rows.device).word), _stream()))
+    return loss[0]
+
+
+def adv_loss(rows: Tensor, n_hist: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, cls: Tensor) -> Tensor:
+    """SentiDebias's discriminator and its loss (reference baselines/senti_debias_plm_module.py:163-167, 275-280) without gradients: rows
+    [N, D], the first ``n_hist`` the history's, ``linear1`` [H, D] / [H], ``linear2`` [O, H] / [O], cls int64 [N] -> the scalar
+    ``mean_hist CE_i + mean_cand CE_i`` with ``CE_i = -log softmax(W2 tanh(W1 x_i + b1) + b2)[(cls_i - 1) mod O]`` — the module writes
+    ``y_true[i, t - 1] = 1``, so class 0 lands on the last column.  No [N, O] one-hot matrix, no loop over the rows.  O <= 64,
+    H <= 1024, D <= 1024; a class outside [0, O) raises at ``check_status``."""
+    rows, n_hist, w1, b1, w2, b2, cls = _adv_operands(rows, n_hist, w1, b1, w2, b2, cls)
+    hidden = torch.empty((rows.shape[0], w1.shape[0]), dtype=torch.float32, device=rows.device)
+    return _adv_forward(rows, n_hist, w1, b1, w2, b2, cls, hidden, None)
+
+
 def axis0_attention_any(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
     """The attention core of ``mha_axis0_any`` on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]; ``stats`` f32 [L0 * B1 * heads * 3]
     receives the softmax statistics the backward reads."""

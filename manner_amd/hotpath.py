@@ -9,6 +9,9 @@
   ``MINERModule`` (reference manner/models/baselines/): the module's own lines between the mirrored leaf classes.
 * ``tanr_forward`` / ``tanr_train_step`` and ``sentirec_forward`` / ``sentirec_train_step`` are ``TANRPLMModule`` and
   ``SentiRecPLMModule``: the auxiliary head over every news row, its loss and SentiRec's diversity regulariser (csrc/aspect.hip).
+* ``senti_debias_forward`` / ``senti_debias_generator_step`` / ``senti_debias_discriminator_step`` are ``SentiDebiasPLMModule``'s
+  generator and its two optimiser steps: the sentiment encoder as a class table, the orthogonality terms, the bias-aware scores and the
+  adversarial discriminator (csrc/debias.hip).
 * ``encode_table`` / ``score_impressions`` are the table architecture (mode T): each unique news is
   encoded once per module into ``[N_news, D]``, impressions are scored by index.  Valid for
   ``use_entities=False`` only.
@@ -357,6 +360,91 @@ def sentirec_train_step(news_encoder, user_encoder, sentiment_predictor, batch: 
     div = (train.senti_div_loss if graph else hip.senti_div_loss)(ragged, cs, hs, hist_off, cand_off, c_max)
     hip.status_arm(rows.device)
     return ce + float(senti_pred_loss_coef) * head + float(senti_div_loss_coef) * div, ragged.detach(), cand_off
+
+
+def _debias_classes(batch: Dict):
+    return batch["x_hist"]["sentiment"].reshape(-1).to(torch.int64), batch["x_cand"]["sentiment"].reshape(-1).to(torch.int64)
+
+
+def _debias_lines(rows: Tensor, n_hist: int, user_encoder, sentiment_encoder, batch: Dict, nb: int):
+    """The lines of SentiDebias's Generator.forward below its encoder calls (reference baselines/senti_debias_plm_module.py:94-146) on the
+    joined rows [N_hist + N_cand, D], history first -> (bias-free ragged scores, combined ragged scores, loss_orth, cand_off, Cmax, the
+    classes of all rows).  The sentiment encoder is its class table [C, D]; the [N, D] sentiment rows are never formed."""
+    ops = train if torch.is_grad_enabled() else hip
+    table = train.class_table(sentiment_encoder.embedding_layer.weight, sentiment_encoder.linear.weight, sentiment_encoder.linear.bias)
+    hist_off = segment_offsets(batch["batch_hist"], nb)
+    cand_off = segment_offsets(batch["batch_cand"], nb)
+    s, c_max = _width(batch, "hist_max", hist_off), _width(batch, "cand_max", cand_off)
+    hist_vec, cand_vec = rows[:n_hist], rows[n_hist:]
+    cls_hist, cls_cand = _debias_classes(batch)
+    cls = torch.cat((cls_hist, cls_cand))
+    dense_of = train.to_dense if torch.is_grad_enabled() and rows.requires_grad else hip.to_dense
+    user_free = user_encoder(dense_of(hist_vec, hist_off, s))
+    user_aware = user_encoder(ops.class_dense(table, cls_hist, hist_off, s))
+    cand_dense = dense_of(cand_vec, cand_off, c_max)
+    dot = train.dot if torch.is_grad_enabled() and (user_free.requires_grad or cand_dense.requires_grad) else hip.dot
+    free = dot(user_free.unsqueeze(1), cand_dense.permute(0, 2, 1)).reshape(-1).index_select(0, train.dense_slots(cand_off, cand_vec.shape[0], c_max))
+    combined = free + ops.class_scores(user_aware, table, cls_cand, cand_off)
+    orth = ops.orth_loss(rows, n_hist, table, cls, user_free, user_aware)
+    return free, combined, orth, cand_off, c_max, cls
+
+
+def _discriminator_params(discriminator):
+    p = (discriminator.linear1.weight, discriminator.linear1.bias, discriminator.linear2.weight, discriminator.linear2.bias)
+    return p if torch.is_grad_enabled() else tuple(t.detach() for t in p)
+
+
+def senti_debias_forward(news_encoder, user_encoder, sentiment_encoder, batch: Dict, dense: bool = True):
+    """SentiDebias's Generator.forward (reference baselines/senti_debias_plm_module.py:85-148) -> (combined_scores, bias_free_scores,
+    loss_orth, clicked_news_vector, candidate_news_vector): the two news-encoder calls on ``batch["x_hist"]["text"]`` /
+    ``batch["x_cand"]["text"]``, ``user_encoder`` (the NRMSUserEncoder of this package) once on the dense history and once on the dense
+    sentiment rows (``class_dense`` of the class table), the three orthogonality terms (``orth_loss``), DotProduct, and the bias-aware
+    scores from the [B, C] products (``class_scores``).  ``sentiment_encoder`` is the module's own SentimentEncoder (``embedding_layer``,
+    ``linear``).  Scores are [B, Cmax] with padded slots exactly 0, or the ragged [sum c_i] vectors with ``dense=False``.  No host
+    synchronisation when the batch carries ``hist_max`` / ``cand_max``."""
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    hist_vec = news_encoder(batch["x_hist"]["text"])
+    cand_vec = news_encoder(batch["x_cand"]["text"])
+    n_hist = hist_vec.shape[0]
+    rows = torch.cat((hist_vec, cand_vec))                        # the operators take the rows as one block, history first
+    free, combined, orth, cand_off, c_max, _ = _debias_lines(rows, n_hist, user_encoder, sentiment_encoder, batch, nb)
+    hip.status_arm(rows.device)
+    if dense:
+        free, combined = _miner_dense(free, cand_off, c_max), _miner_dense(combined, cand_off, c_max)
+    return combined, free, orth, hist_vec, cand_vec
+
+
+def senti_debias_generator_step(news_encoder, user_encoder, sentiment_encoder, discriminator, batch: Dict, alpha: float, beta: float):
+    """The generator half of SentiDebiasPLMModule.training_step (reference baselines/senti_debias_plm_module.py:339-343):
+    ``CrossEntropyLoss(combined_scores, y_true) + beta * loss_orth - alpha * (adversarial_loss(history) + adversarial_loss(candidates))``
+    with both news sets through ONE encoder call, the cross-entropy from the ragged combined scores
+    (``train.model_step_loss(supcon=False, c_max=...)``) and the discriminator with its loss as ``adv_loss`` on the rows as they lie.
+    ``discriminator`` is the module's own (``linear1``, ``linear2``); frozen by ``toggle_optimizer`` it receives no gradient and only the
+    rows' is formed.  Returns (g_loss, bias-free ragged scores [sum c_i] detached, cand_off) — ``manual_backward``, the two optimisers,
+    the logging and the metrics stay the caller's.  Under ``torch.no_grad()`` the same kernels run without saving anything.  No host
+    synchronisation when the batch carries ``hist_max`` / ``cand_max``."""
+    nb = batch["users"].numel() if "users" in batch and batch["users"] is not None else int(batch["batch_cand"].max()) + 1
+    hip.status_poll(batch["batch_cand"].device)
+    rows, n_hist = _encode_joined(news_encoder, batch["x_hist"]["text"], batch["x_cand"]["text"])
+    free, combined, orth, cand_off, c_max, cls = _debias_lines(rows, n_hist, user_encoder, sentiment_encoder, batch, nb)
+    ce, _ = train.model_step_loss(combined, batch["labels"].to(torch.float32), cand_off, supcon=False, c_max=c_max)
+    adv = (train.adv_loss if torch.is_grad_enabled() else hip.adv_loss)(rows, n_hist, *_discriminator_params(discriminator), cls)
+    hip.status_arm(rows.device)
+    return ce + float(beta) * orth - float(alpha) * adv, free.detach(), cand_off
+
+
+def senti_debias_discriminator_step(news_encoder, discriminator, batch: Dict):
+    """The discriminator half of SentiDebiasPLMModule.training_step (reference baselines/senti_debias_plm_module.py:353-355): the news
+    rows re-encoded under the generator's updated weights — ONE encoder call, alone: the reference's second generator pass also runs the
+    user encoders, the scores and the orthogonality terms, which nothing reads there — detached, and ``d_loss`` = ``adv_loss`` over
+    them with gradients into the discriminator's four parameters only."""
+    hip.status_poll(batch["batch_cand"].device)
+    rows, n_hist = _encode_joined(news_encoder, batch["x_hist"]["text"], batch["x_cand"]["text"])
+    cls = torch.cat(_debias_classes(batch))
+    loss = (train.adv_loss if torch.is_grad_enabled() else hip.adv_loss)(rows.detach(), n_hist, *_discriminator_params(discriminator), cls)
+    hip.status_arm(rows.device)
+    return loss
 
 
 def a_train_step(news_encoder, batch: Dict, temperature: float = 0.1):

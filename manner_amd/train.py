@@ -734,6 +734,160 @@ def senti_div_loss(scores: Tensor, cand_score: Tensor, hist_score: Tensor, hist_
     return _SentiDiv.apply(*hip._senti_div_operands(scores, cand_score, hist_score, hist_off, cand_off, c_max))
 
 
+class _MaskRowZero(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table: Tensor):
+        return table.view_as(table)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        g = g.clone()
+        g[0].zero_()
+        return g
+
+
+def class_table(embedding_weight: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
+    """The C distinct outputs of SentiDebias's SentimentEncoder (reference baselines/senti_debias_plm_module.py:41-42),
+    ``tanh(linear(embedding.weight))`` [C, D] by ``linear_tanh`` on the C rows.  Row 0 (``padding_idx = 0``) is read as it lies and receives
+    no gradient into the embedding; its ``tanh(b)`` still sends gradient into the linear."""
+    graph = torch.is_grad_enabled() and (embedding_weight.requires_grad or weight.requires_grad or bias.requires_grad)
+    if not graph:
+        return hip.linear_tanh(embedding_weight.detach(), weight.detach(), bias.detach())
+    return linear_tanh(_MaskRowZero.apply(embedding_weight) if embedding_weight.requires_grad else embedding_weight, weight, bias)
+
+
+class _OrthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows: Tensor, n_hist: int, table: Tensor, cls: Tensor, user_free: Tensor, user_aware: Tensor):
+        means = torch.empty(2, dtype=torch.float32, device=rows.device)
+        loss = hip._orth_forward(rows, n_hist, table, cls, user_free, user_aware, means)
+        ctx.save_for_backward(rows, table, cls, user_free, user_aware, means)
+        ctx.n_hist = n_hist
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        rows, table, cls, user_free, user_aware, means = ctx.saved_tensors
+        need_rows, _, need_table, _, need_free, need_aware = ctx.needs_input_grad
+        n, d = rows.shape
+        c, b = table.shape[0], user_free.shape[0]
+        d_rows = torch.empty_like(rows) if need_rows else None
+        d_table = torch.empty_like(table) if need_table else None
+        d_free = torch.empty_like(user_free) if need_free else None
+        d_aware = torch.empty_like(user_aware) if need_aware else None
+        lib = _lib.load()
+        with torch.cuda.device(rows.device):
+            g = _f32(g, "grad").reshape(1)                       # stays on the device: nothing is read back
+            need = int(lib.manner_hip_orth_loss_backward_workspace_bytes(n, d, c)) if need_table else 0
+            ws = hip._workspace(need, rows.device) if need else None
+            _lib.check(lib.manner_hip_orth_loss_backward(hip._ptr(g), hip._ptr(means), hip._ptr(rows), n, ctx.n_hist, hip._ptr(table), hip._ptr(cls),
+                                                         hip._ptr(user_free), hip._ptr(user_aware), b, d, c, hip._ptr(d_rows), hip._ptr(d_table),
+                                                         hip._ptr(d_free), hip._ptr(d_aware), hip._ptr(ws), need, hip._stream()))
+        return d_rows, None, d_table, None, d_free, d_aware
+
+
+def orth_loss(rows: Tensor, n_hist: int, table: Tensor, cls: Tensor, user_free: Tensor, user_aware: Tensor) -> Tensor:
+    """``hip.orth_loss`` with autograd into the rows, the class table and the two user vectors; the table's gradient is a per-class sum
+    over chunks of ascending rows added in order.  A zero vector receives torch's zero gradient through its norm."""
+    return _OrthLoss.apply(*hip._orth_operands(rows, n_hist, table, cls, user_free, user_aware))
+
+
+class _ClassDense(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table: Tensor, cls: Tensor, off: Tensor, width: int):
+        ctx.save_for_backward(cls, off)
+        ctx.dims = (width, table.shape[1], table.shape[0])
+        return hip._class_dense_forward(table, cls, off, width)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        cls, off = ctx.saved_tensors
+        width, d, c = ctx.dims
+        b = off.numel() - 1
+        d_table = torch.empty((c, d), dtype=torch.float32, device=g.device)
+        lib = _lib.load()
+        with torch.cuda.device(g.device):
+            g = _f32(g, "grad").contiguous()
+            need = int(lib.manner_hip_class_dense_backward_workspace_bytes(b, width, d, c))
+            ws = hip._workspace(need, g.device)
+            _lib.check(lib.manner_hip_class_dense_backward(hip._ptr(g), hip._ptr(cls), hip._ptr(off), cls.numel(), b, width, d, c, hip._ptr(d_table),
+                                                           hip._ptr(ws), need, hip._stream()))
+        return d_table, None, None, None
+
+
+def class_dense(table: Tensor, cls: Tensor, off: Tensor, width: int) -> Tensor:
+    """``hip.class_dense`` with autograd into the class table."""
+    return _ClassDense.apply(*hip._class_dense_operands(table, cls, off, width))
+
+
+class _ClassScores(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, user: Tensor, table: Tensor, cls: Tensor, off: Tensor):
+        ctx.save_for_backward(user, table, cls, off)
+        return hip._class_scores_forward(user, table, cls, off)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        user, table, cls, off = ctx.saved_tensors
+        need_user, need_table = ctx.needs_input_grad[:2]
+        b, d = user.shape
+        c = table.shape[0]
+        d_user = torch.empty_like(user) if need_user else None
+        d_table = torch.empty_like(table) if need_table else None
+        lib = _lib.load()
+        with torch.cuda.device(user.device):
+            g = _f32(g, "grad").contiguous()
+            need = int(lib.manner_hip_class_scores_workspace_bytes(b, c))
+            ws = hip._workspace(need, user.device)
+            _lib.check(lib.manner_hip_class_scores_backward(hip._ptr(g), hip._ptr(user), hip._ptr(table), hip._ptr(cls), hip._ptr(off), cls.numel(), b,
+                                                            d, c, hip._ptr(d_user), hip._ptr(d_table), hip._ptr(ws), need, hip._stream()))
+        return d_user, d_table, None, None
+
+
+def class_scores(user: Tensor, table: Tensor, cls: Tensor, off: Tensor) -> Tensor:
+    """``hip.class_scores`` with autograd into the user vectors and the class table, from the per-(user, class) sums of the upstream
+    gradient."""
+    return _ClassScores.apply(*hip._class_scores_operands(user, table, cls, off))
+
+
+class _AdvLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows: Tensor, n_hist: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, cls: Tensor):
+        hidden = torch.empty((rows.shape[0], w1.shape[0]), dtype=torch.float32, device=rows.device)
+        saved = torch.empty((rows.shape[0], w2.shape[0]), dtype=torch.float32, device=rows.device)      # (p - y) / rows of the segment
+        loss = hip._adv_forward(rows, n_hist, w1, b1, w2, b2, cls, hidden, saved)
+        ctx.save_for_backward(rows, w1, w2, hidden, saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        rows, w1, w2, hidden, saved = ctx.saved_tensors
+        need_rows, _, need_w1, need_b1, need_w2, need_b2, _ = ctx.needs_input_grad
+        n, d = rows.shape
+        h, o = w1.shape[0], w2.shape[0]
+        d_rows = torch.empty_like(rows) if need_rows else None
+        d_w1 = torch.empty_like(w1) if need_w1 else None
+        d_b1 = torch.empty(h, dtype=torch.float32, device=rows.device) if need_b1 else None
+        d_w2 = torch.empty_like(w2) if need_w2 else None
+        d_b2 = torch.empty(o, dtype=torch.float32, device=rows.device) if need_b2 else None
+        lib = _lib.load()
+        with torch.cuda.device(rows.device):
+            g = _f32(g, "grad").reshape(1)                       # stays on the device: nothing is read back
+            need = int(lib.manner_hip_adv_loss_backward_workspace_bytes(n, d, h, o))
+            ws = hip._workspace(need, rows.device)
+            _lib.check(lib.manner_hip_adv_loss_backward(hip._ptr(g), hip._ptr(rows), n, hip._ptr(w1), hip._ptr(w2), hip._ptr(hidden), hip._ptr(saved),
+                                                        d, h, o, hip._ptr(d_rows), hip._ptr(d_w1), hip._ptr(d_b1), hip._ptr(d_w2), hip._ptr(d_b2),
+                                                        hip._ptr(ws), need, hip._stream()))
+        return d_rows, None, d_w1, d_b1, d_w2, d_b2, None
+
+
+def adv_loss(rows: Tensor, n_hist: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, cls: Tensor) -> Tensor:
+    """``hip.adv_loss`` with autograd into the rows and the discriminator's four parameters.  In the generator step the discriminator is
+    frozen and only the rows' gradient is formed, in the discriminator step the rows are detached and only the four parameter gradients:
+    both are the bits of the full backward."""
+    return _AdvLoss.apply(*hip._adv_operands(rows, n_hist, w1, b1, w2, b2, cls))
+
+
 class _Axis0Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv: Tensor, heads: int):
