@@ -23,30 +23,7 @@ constexpr int AS_WG_ROWS = 8, AS_MAX_WG = 512;           // rows a workgroup tak
 constexpr int AS_CHUNK_ROWS = 32, AS_MAX_CHUNKS = 128;   // weight gradient: rows per partial sum at least; partial sums at most
 constexpr size_t AS_STAGE_BYTES = 128 * 1024;            // a weight up to here is staged in LDS (160 KB per CU), a larger one is read through L2
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// all 256 threads: the weight [O, D] into LDS, 16 bytes per lane where the pointer allows; ends with a barrier
-__device__ __forceinline__ void stage_weight(const float* __restrict__ W, int n, float* wl) {
-  const int n4 = (reinterpret_cast<uintptr_t>(W) & 15u) == 0 ? n / 4 : 0;
-  for (int i = threadIdx.x; i < n4; i += 256) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(W)[i];
-  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) wl[i] = W[i];
-  __syncthreads();
-}
 
 // ---------------------------------------------------------------- the row heads, forward
 // MODE 0: cross-entropy, the weight staged in LDS; 1: cross-entropy, the weight read where it lies; 2: L1 (O == 1, the weight row in

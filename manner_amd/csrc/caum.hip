@@ -38,17 +38,7 @@ static_assert(CA_KT * CA_MAX_DH <= CA_LDS, "a tile of the largest head fits");
 static_assert(CA_OT * CA_WAVES == CA_BLOCK && CA_WAVES == 4 && CA_KS % CA_WAVES == 0, "lin_kernel: thread = (output feature, K quarter)");
 static_assert(CA_MAX_S % CA_WAVE == 0, "one wave holds a user's scores, CA_MAX_S / CA_WAVE per lane");
 static_assert(CA_KT <= CA_BLOCK, "the statistics of a tile fit one entry per thread");
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = CA_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, CA_WAVE);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = CA_WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, CA_WAVE));
-  return v;
-}
+static_assert(CA_WAVE == 64, "common.h's wsum / wmax reduce 64 lanes");
 
 // ---------------------------------------------------------------- window / candidate operands
 // grid (B S): a1[r] = [xd[b, s-1], xd[b, s], xd[b, s+1], cd[b]] (circular shift, user_encoder.py:128-144), a2[r] = [cd[b], xd[b, s]]
@@ -256,9 +246,9 @@ int launch_colsum(const float* dy, int ldy, int64_t R, int O, float* db, hipStre
   return MANNER_HIP_OK;
 }
 
-// ---------------------------------------------------------------- axis-0 attention at any head dim
+// ---------------------------------------------------------------- axis-0 attention at any head dim (the fixed-dim family: axis0.hip)
 // qkv [N, E, 3D] (q | k | v), attention along the N axis for each (slot e, head) pair; dh = D / heads is a run-time value under the
-// compile-time register width DHP.  The arithmetic is that of train_small.hip's axis0_fwd_kernel / axis0_bwd_*: q scaled first, online
+// compile-time register width DHP.  The arithmetic is that of axis0.hip's axis0_fwd_kernel / axis0_bwd_*: q scaled first, online
 // softmax over the keys in ascending order.  Threads are filled at small N: a workgroup takes P pairs, thread = (pair, row), and the
 // K / V rows (backward-kv: the Q / d out rows) of all its pairs sit in LDS (A0Plan: P * N * dh <= CA_LDS floats per operand).  A pair
 // that does not fit, or N > 256, runs alone in its workgroups with the other side streamed in tiles of CA_KT rows.

@@ -50,6 +50,33 @@ static inline int current_device_slot() {
 }
 int device_cus();   // compute units of the current device (gemm.hip)
 
+// ------------------------------------------------------------------ wave helpers
+// The one copy of what the kernel files share.  wsum / wmax: xor butterfly over the 64 lanes of a wave, every lane ends with the result.
+__device__ __forceinline__ float wsum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wsum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wmax(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
+// all 256 threads: a weight of n floats into LDS, 16 bytes per lane where the pointer allows; ends with a barrier
+__device__ __forceinline__ void stage_weight(const float* __restrict__ W, int n, float* wl) {
+  const int n4 = (reinterpret_cast<uintptr_t>(W) & 15u) == 0 ? n / 4 : 0;
+  for (int i = threadIdx.x; i < n4; i += 256) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(W)[i];
+  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) wl[i] = W[i];
+  __syncthreads();
+}
+
 // ------------------------------------------------------------------ GEMM (gemm.hip)
 enum Epilogue { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_NORM = 3, EPI_NORM_GELU = 4, EPI_NRES = 5,
                 EPI_BIAS_RES_F32 = 6 /* bf16 operands, f32 residual and output: the bf16x3 parity mode */,
@@ -184,6 +211,11 @@ int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, in
 // ctx_cls [n_news, H].
 int attention_cls(DType dt, const void* qcls, const void* kv, void* ctx_cls, const int32_t* cu, int64_t n_news,
                   int heads, int H, hipStream_t stream);
+
+// ------------------------------------------------------------------ axis-0 attention, fixed head dims (axis0.hip)
+// nn.MultiheadAttention(batch_first=False) core on [N, E, 3D] projections = [q | k | v]: att [N, E, D], attention along axis 0 for each
+// (slot e, head); head dims 4, 8, 10, 16, 32, 48, 64.  train_tiles: the training column of the key-tile table, else the inference one.
+int launch_axis0_attention(const float* qkv, float* att, int64_t N, int64_t E, int D, int heads, bool train_tiles, hipStream_t stream);
 
 // ------------------------------------------------------------------ f32 matrix-core linear (caum.hip)
 // y [R, O] = act(bias + x W^T) on wlin_kernel: x rows ldx apart, W [O, K] rows ldw apart, y rows ldy apart, bias may be NULL; R >= 1.

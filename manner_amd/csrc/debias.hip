@@ -27,26 +27,8 @@ constexpr int DB_CHUNK_ROWS = 32, DB_MAX_CHUNKS = 128;   // binned sums: rows pe
 constexpr size_t DB_STAGE_BYTES = 128 * 1024;            // a W2 up to here is staged in LDS, a larger one is read through L2
 constexpr float DB_EPS = 1e-8f;
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }      // torch's sign: 0 at 0 and at NaN
 
-// all 256 threads: a weight of n floats into LDS, 16 bytes per lane where the pointer allows; ends with a barrier
-__device__ __forceinline__ void stage_weight(const float* __restrict__ W, int n, float* wl) {
-  const int n4 = (reinterpret_cast<uintptr_t>(W) & 15u) == 0 ? n / 4 : 0;
-  for (int i = threadIdx.x; i < n4; i += 256) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(W)[i];
-  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) wl[i] = W[i];
-  __syncthreads();
-}
 
 // all 256 threads: the sum of the threads' `a` in a fixed tree
 __device__ __forceinline__ double block_sum(double a, double* sm) {

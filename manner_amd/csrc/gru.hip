@@ -31,13 +31,7 @@ constexpr int GR_TT = 32;            // tile edge of the transpose
 constexpr int GR_ALIGN = 64;         // floats every saved / workspace buffer is aligned to
 static_assert(GR_OT * GR_WAVES == GR_BLOCK && GR_WAVES == 4 && GR_KS % GR_WAVES == 0, "proj_kernel: thread = (output feature, K quarter)");
 static_assert(GR_ROWS <= GR_WAVE, "lane rr of a wave finishes batch row rr");
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = GR_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, GR_WAVE);
-  return v;
-}
-__device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
+static_assert(GR_WAVE == 64, "common.h's wsum reduces 64 lanes");
 
 // ---------------------------------------------------------------- input projection
 // gi[r, o] = b[o] + sum_k x[b, t, k] W[o, k], r = b S + t; x[b, t, :] at x + b xsb + t xss, read as zeros where t >= len[b].

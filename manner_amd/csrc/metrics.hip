@@ -302,8 +302,7 @@ __global__ __launch_bounds__(256) void eval_loss_kernel(const float* __restrict_
   const int64_t pad = mode == 1 ? c_max - (c1 - c0) : 0;
   float mx = pad > 0 ? 0.f : -INFINITY;
   for (int64_t j = c0 + lane; j < c1; j += 64) mx = fmaxf(mx, scores[j] * inv_t);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wmax(mx);
   float se = 0.f, sp = 0.f, np = 0.f;
   for (int64_t j = c0 + lane; j < c1; j += 64) {
     const float v = scores[j] * inv_t - mx;          // contraction is off in this kernel: the row maximum gives exactly 0

@@ -19,17 +19,6 @@ constexpr int MN_MAX_DC = 1024, MN_MAX_S = 256, MN_MAX_K = 64, MN_MAX_D = 1024;
 constexpr int MN_J = MN_MAX_D / 64;            // row elements per lane
 static_assert(MN_MAX_DC == MN_MAX_D, "one row holder for both widths");
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ---------------------------------------------------------------- category bias
 // Unit rows, one wave per row r of [candidates (T rows) | history (NH rows)]: unit[r, :] = e / ||e||, e = dropout(table[cat[r], :]).

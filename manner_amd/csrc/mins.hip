@@ -36,12 +36,6 @@ constexpr int PJ_BLOCK = 256, PJ_WAVES = 4, PJ_ROWS = 8, PJ_OT = 64, PJ_KS = 128
 static_assert(PJ_OT * PJ_WAVES == PJ_BLOCK && PJ_KS % PJ_WAVES == 0, "cproj_kernel: thread = (output feature, K quarter)");
 static_assert(CG_HP % 4 == 0, "the h rows are read as float4");
 
-__device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------- input projection
 // gi[r, o] = b[o] + sum_k x[b, t, c I + k] W[o, k], r = (b S + t) C + c; the row is read as zeros where t >= len[b].  `xs` [R, K]
@@ -283,7 +277,7 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_bwd_kernel(const float* __restric
   }
 }
 
-// ---------------------------------------------------------------- axis-0 attention, 65 <= head dim <= 128
+// ---------------------------------------------------------------- axis-0 attention, 65 <= head dim <= 128 (the fixed-dim family: axis0.hip)
 constexpr int AW_BLOCK = 256, AW_WAVES = 4;      // a wave per own row: AW_WAVES rows of one (slot, head) pair per workgroup
 constexpr int AW_KT = 32;                        // rows of the other side per LDS tile (2 x 16 KiB)
 constexpr int AW_DH = 128, AW_MIN_DH = 65;

@@ -20,11 +20,6 @@ constexpr int PA_SB = 8;         // history rows per workgroup of the second bac
 constexpr int TA_CT = 8;         // candidates per tile of the target-aware kernels
 constexpr int WG_MAX_GROUPS = 16, WG_ROWS = 64;      // weight gradient: row groups, least rows per group
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // N wave sums at once: the N exchange chains of a round are independent, so their cross-lane latency overlaps
 template <int N>
 __device__ __forceinline__ void wsum_n(float (&v)[N]) {
@@ -33,11 +28,6 @@ __device__ __forceinline__ void wsum_n(float (&v)[N]) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], o, 64);
   }
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float v) {

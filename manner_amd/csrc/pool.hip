@@ -77,16 +77,6 @@ __device__ __forceinline__ float rowsum16(float v) {
   v += dpp_mov<0x140>(v);    // row_mirror
   return v;
 }
-__device__ __forceinline__ float wave_max64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // k with 2^k * m in [2^13, 2^14) for a finite m > 0 (k clamped to [-114, 126]); 0 for m = 0, inf or nan
 __device__ __forceinline__ int scale_exponent(float m) {
   const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu);
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(256) void pool_w_max_kernel(const float* __restrict
     const f32x4 v = *reinterpret_cast<const f32x4*>(W + i);                       // n % 4 == 0 (D % 32 == 0), 16-byte aligned rows
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));    // fmaxf drops NaNs: a NaN weight gives NaN products anyway
   }
-  m = wave_max64(m);
+  m = wmax(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) atomicMax(wmax_bits, __builtin_bit_cast(uint32_t, fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
@@ -367,10 +357,10 @@ __global__ __launch_bounds__(64 * NW, 2) void pool_fused_kernel(
   const int rows = 16 * SP;                             // <= 128
   const float l0 = lane < rows ? lg[bl * rows + lane] : -INFINITY;
   const float l1 = lane + 64 < rows ? lg[bl * rows + 64 + lane] : -INFINITY;
-  const float mx = wave_max64(fmaxf(l0, l1));
+  const float mx = wmax(fmaxf(l0, l1));
   float wgt = 0.f;                                      // stays 0 for a batch element past B (all logits -inf): nothing is written for it
   if (mx != -INFINITY) {
-    const float den = wave_sum64(expf(l0 - mx) + expf(l1 - mx));
+    const float den = wsum(expf(l0 - mx) + expf(l1 - mx));
     wgt = (expf(p - mx) / den) * inv_x;                 // the row's scale folded into its weight
   }
 

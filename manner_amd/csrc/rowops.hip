@@ -10,11 +10,6 @@ namespace {
 constexpr int MAX_H = 1024;          // 4 x float4 per lane
 constexpr int VEC_PER_LANE = MAX_H / 256;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---- lengths: one wave per news; validates that mask is a 0/1 prefix with 1 <= len <= max_len (the caller's per-row limit)
 __global__ __launch_bounds__(256) void lengths_kernel(const int64_t* __restrict__ mask, int64_t n_news,
@@ -98,7 +93,7 @@ __device__ __forceinline__ void wave_layernorm_store(f32x4 v[VEC_PER_LANE], int 
 #pragma unroll
   for (int i = 0; i < VEC_PER_LANE; ++i)
     if ((i * 64 + lane) * 4 < H) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  const float mean = wave_sum(s) / (float)H;
+  const float mean = wsum(s) / (float)H;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < VEC_PER_LANE; ++i)
@@ -106,7 +101,7 @@ __device__ __forceinline__ void wave_layernorm_store(f32x4 v[VEC_PER_LANE], int 
 #pragma unroll
       for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; q += d * d; }
     }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + eps);
+  const float rstd = 1.0f / sqrtf(wsum(q) / (float)H + eps);
 #pragma unroll
   for (int i = 0; i < VEC_PER_LANE; ++i) {
     const int c = (i * 64 + lane) * 4;
@@ -249,7 +244,7 @@ __global__ __launch_bounds__(256) void embed_raw_kernel(
         store_vec<TE>(raw + (size_t)(start + t) * H + c, v[i]);
       }
     }
-    const float mean = wave_sum(s) / (float)H;
+    const float mean = wsum(s) / (float)H;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VEC_PER_LANE; ++i)
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(256) void embed_raw_kernel(
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; q += d * d; }
       }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + eps);
+    const float rstd = 1.0f / sqrtf(wsum(q) / (float)H + eps);
     if (lane == 0) mr[start + t] = float2{mean, rstd};
   }
 }
@@ -305,7 +300,7 @@ __global__ __launch_bounds__(256) void fold_ln_kernel(const float* __restrict__ 
     s1 += (float)f;
     s2 = fmaf(beta[k], x, s2);
   }
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
+  s1 = wsum(s1); s2 = wsum(s2);
   if (lane == 0) { c1[n] = s1; c2[n] = bias[n] + s2; }
 }
 

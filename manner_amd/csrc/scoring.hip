@@ -10,16 +10,6 @@
 namespace manner {
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // dot of a table row with a vector held in LDS; D % 4 == 0
 __device__ __forceinline__ float row_dot(const float* __restrict__ row, const float* vec, int D, int lane) {
@@ -29,7 +19,7 @@ __device__ __forceinline__ float row_dot(const float* __restrict__ row, const fl
     const f32x4 u = *reinterpret_cast<const f32x4*>(vec + c);
     a += (x[0] * u[0] + x[1] * u[1]) + (x[2] * u[2] + x[3] * u[3]);
   }
-  return wave_sum(a);
+  return wsum(a);
 }
 
 // ---------------------------------------------------------------- K9 + K10 + K12 fused
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(256) void score_late_fusion_kernel(
       a0 += (x0[0] * u[0] + x0[1] * u[1]) + (x0[2] * u[2] + x0[3] * u[3]);
       a1 += (x1[0] * u[0] + x1[1] * u[1]) + (x1[2] * u[2] + x1[3] * u[3]);
     }
-    a0 = wave_sum(a0); a1 = wave_sum(a1);
+    a0 = wsum(a0); a1 = wsum(a1);
     if (lane == 0) { out[j] = a0; if (two) out[j + 4] = a1; }
   }
 }
@@ -171,7 +161,7 @@ __device__ __forceinline__ void score_rows_body(
 #pragma unroll
       for (int k = 0; k < NCB; ++k)
         a[q] += (x[q][k][0] * u[k][0] + x[q][k][1] * u[k][1]) + (x[q][k][2] * u[k][2] + x[q][k][3] * u[k][3]);
-      a[q] = wave_sum(a[q]);
+      a[q] = wsum(a[q]);
     }
     if (lane == 0) {
 #pragma unroll
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(256) void score_late_fusion_f16_kernel(
     if (mu) { const float m = mu[c]; u += m; cp = fmaf(u, m, cp); }
     user[c] = u;
   }
-  cp = wave_sum(cp);
+  cp = wsum(cp);
   if (lane == 0) cpart[wave] = cp;
   __syncthreads();
   const float konst = (cpart[0] + cpart[1]) + (cpart[2] + cpart[3]);          // <w, mu> (0 without centring)
@@ -255,7 +245,7 @@ __global__ __launch_bounds__(256) void score_late_fusion_f16_kernel(
       a0 += dot8(x0, u0, u1);
       a1 += dot8(x1, u0, u1);
     }
-    a0 = wave_sum(a0); a1 = wave_sum(a1);
+    a0 = wsum(a0); a1 = wsum(a1);
     if (lane == 0) { out[j] = a0 + konst; if (two) out[j + 4] = a1 + konst; }
   }
 }
@@ -339,7 +329,7 @@ __global__ __launch_bounds__(256) void score_late_fusion_f16_rows_kernel(
     if (mu) { const float m = mu[c]; u += m; cp = fmaf(u, m, cp); }
     user[c] = u;
   }
-  cp = wave_sum(cp);
+  cp = wsum(cp);
   if (lane == 0) cpart[wave] = cp;
   __syncthreads();
   const float konst = (cpart[0] + cpart[1]) + (cpart[2] + cpart[3]);          // <w, mu> (0 without centring)
@@ -450,7 +440,7 @@ __global__ __launch_bounds__(256) void dot_rows_kernel(const float* __restrict__
   } else {
     for (int d = lane; d < D; d += 64) a += x[d] * u[d];
   }
-  a = wave_sum(a);
+  a = wsum(a);
   if (lane == 0) out[p] = a;
 }
 // general strides (e.g. a materialised [B,D,C] tensor): one thread per candidate, coalesced over c
@@ -503,13 +493,13 @@ __global__ __launch_bounds__(256) void pool_apply_kernel(const float* __restrict
   const float* lg = logits + b * S;
   float mx = -INFINITY;
   for (int64_t s = threadIdx.x; s < S; s += 256) mx = fmaxf(mx, lg[s]);
-  mx = wave_max(mx);
+  mx = wmax(mx);
   if (lane == 0) red[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float den = 0.f;
   for (int64_t s = threadIdx.x; s < S; s += 256) den += expf(lg[s] - mx);
-  den = wave_sum(den);
+  den = wsum(den);
   if (lane == 0) red[4 + wave] = den;
   __syncthreads();
   den = (red[4] + red[5]) + (red[6] + red[7]);
@@ -570,11 +560,11 @@ __global__ __launch_bounds__(256) void zscore_fuse_kernel(const float* __restric
       float a = 0.f;
 #pragma unroll
       for (int t = 0; t < ZC; ++t) if (c0 + lane + 64 * t < c1) a += v[k][t];
-      const float mean = wave_sum(a) / cn;
+      const float mean = wsum(a) / cn;
       float q = 0.f;
 #pragma unroll
       for (int t = 0; t < ZC; ++t) if (c0 + lane + 64 * t < c1) { const float d = v[k][t] - mean; q += d * d; }
-      const float sd = sqrtf(wave_sum(q) / (cn - 1.0f));
+      const float sd = sqrtf(wsum(q) / (cn - 1.0f));
 #pragma unroll
       for (int t = 0; t < ZC; ++t) {
         const float z = (v[k][t] - mean) / sd;
@@ -594,10 +584,10 @@ __global__ __launch_bounds__(256) void zscore_fuse_kernel(const float* __restric
     const float* s = scores + (int64_t)k * plane_stride;
     float a = 0.f;
     for (int64_t j = c0 + lane; j < c1; j += 64) a += s[j];
-    const float mean = wave_sum(a) / cn;               // sum(scores, dim=1) / cand_size  (:147)
+    const float mean = wsum(a) / cn;               // sum(scores, dim=1) / cand_size  (:147)
     float q = 0.f;
     for (int64_t j = c0 + lane; j < c1; j += 64) { const float d = s[j] - mean; q += d * d; }
-    const float sd = sqrtf(wave_sum(q) / (cn - 1.0f)); // torch.std: unbiased; c == 1 -> NaN  (:143)
+    const float sd = sqrtf(wsum(q) / (cn - 1.0f)); // torch.std: unbiased; c == 1 -> NaN  (:143)
     for (int64_t j = c0 + lane; j < c1; j += 64) {
       const float z = (s[j] - mean) / sd;
       out[j] = k == 0 ? z : out[j] + wk * z;           // scores += w * z  (:102,:107)
@@ -658,7 +648,7 @@ __global__ __launch_bounds__(256) void rank_ndcg_kernel(const float* __restrict_
     }
   }
   if (ndcg && l) {
-    dcg = wave_sum(dcg); idcg = wave_sum(idcg); pos = wave_sum(pos);
+    dcg = wsum(dcg); idcg = wsum(idcg); pos = wsum(pos);
     if (lane == 0) ndcg[i] = pos == 0.f ? 0.f : dcg / idcg;   // empty_target_action="neg" -> 0
   }
   if (mrr && l) {
@@ -724,10 +714,10 @@ __global__ __launch_bounds__(256) void score_fuse_rank_kernel(
         const float* s = scratch + (int64_t)k * total + c0;
         float a = 0.f;
         for (int j = lane; j < c; j += 64) a += s[j];
-        const float mean = wave_sum(a) / cn;
+        const float mean = wsum(a) / cn;
         float q = 0.f;
         for (int j = lane; j < c; j += 64) { const float d = s[j] - mean; q += d * d; }
-        const float sd = sqrtf(wave_sum(q) / (cn - 1.0f));
+        const float sd = sqrtf(wsum(q) / (cn - 1.0f));
         for (int j = lane; j < c; j += 64) {
           const float z = (s[j] - mean) / sd;
           o[j] = k == 0 ? z : o[j] + wk * z;
@@ -761,7 +751,7 @@ __global__ __launch_bounds__(256) void score_fuse_rank_kernel(
       }
     }
     if (ndcg && l) {
-      dcg = wave_sum(dcg); idcg = wave_sum(idcg); pos = wave_sum(pos);
+      dcg = wsum(dcg); idcg = wsum(idcg); pos = wsum(pos);
       if (lane == 0) ndcg[b] = pos == 0.f ? 0.f : dcg / idcg;
     }
     if (mrr && l) {
@@ -786,10 +776,10 @@ __global__ __launch_bounds__(256) void score_fuse_rank_kernel(
         const float* s = planes + k * PC_CAP;
         float a = 0.f;
         for (int j = lane; j < c; j += 64) a += s[j];
-        const float mean = wave_sum(a) / cn;               // sum(scores, dim=1) / cand_size  (:147)
+        const float mean = wsum(a) / cn;               // sum(scores, dim=1) / cand_size  (:147)
         float q = 0.f;
         for (int j = lane; j < c; j += 64) { const float d = s[j] - mean; q += d * d; }
-        const float sd = sqrtf(wave_sum(q) / (cn - 1.0f)); // torch.std: unbiased; c == 1 -> NaN  (:143)
+        const float sd = sqrtf(wsum(q) / (cn - 1.0f)); // torch.std: unbiased; c == 1 -> NaN  (:143)
         for (int j = lane; j < c; j += 64) {
           const float z = (s[j] - mean) / sd;
           fsm[j] = k == 0 ? z : fsm[j] + wk * z;           // scores += w * z  (:102,:107)
@@ -836,7 +826,7 @@ __global__ __launch_bounds__(256) void score_fuse_rank_kernel(
     pos += lsm[a];
   }
   if (ndcg) {
-    dcg = wave_sum(dcg); idcg = wave_sum(idcg); pos = wave_sum(pos);
+    dcg = wsum(dcg); idcg = wsum(idcg); pos = wsum(pos);
     if (lane == 0) ndcg[b] = pos == 0.f ? 0.f : dcg / idcg;   // empty_target_action="neg" -> 0
   }
   if (mrr && lane == 0) {
@@ -876,7 +866,7 @@ __global__ __launch_bounds__(256) void aspect_metrics_kernel(const int32_t* __re
   if (div) {
     float h = 0.f;
     if (top_cnt > 0 && lane < num_classes) { const float p = (float)top_cnt / (float)n_top; h = -p * logf(p); }
-    h = wave_sum(h);
+    h = wsum(h);
     if (lane == 0) div[i] = any ? h / logf((float)num_classes) : 0.f;
   }
   if (pers) {
@@ -884,7 +874,7 @@ __global__ __launch_bounds__(256) void aspect_metrics_kernel(const int32_t* __re
     for (int64_t j = hist_off[i]; j < hist_off[i + 1]; ++j) hist_cnt += hist_aspect[j] == lane ? 1 : 0;
     float mn = lane < num_classes ? (float)min(top_cnt, hist_cnt) : 0.f;
     float mxv = lane < num_classes ? (float)max(top_cnt, hist_cnt) : 0.f;
-    mn = wave_sum(mn); mxv = wave_sum(mxv);
+    mn = wsum(mn); mxv = wsum(mxv);
     if (lane == 0) pers[i] = any ? mn / mxv : 0.f;
   }
 }

@@ -52,11 +52,6 @@ __device__ __forceinline__ void put16x8(const Out16& o, size_t idx, const float*
   }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------------ embeddings
 // e[cu[n]+t] = word[id] + pos[t + pos_offset] + type[0]            (modeling_bert.py:68-108 without LN / dropout)
@@ -151,7 +146,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     v[i] = c < H ? row[c] : 0.f;
     s += v[i];
   }
-  const float mean = wave_sum(s) / (float)H;
+  const float mean = wsum(s) / (float)H;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAX; ++i) {
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     const float d = c < H ? v[i] - mean : 0.f;
     q = fmaf(d, d, q);
   }
-  const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);      // biased variance, as F.layer_norm
+  const float rstd = rsqrtf(wsum(q) / (float)H + eps);      // biased variance, as F.layer_norm
   if (lane == 0) stats[m] = float2{mean, rstd};
   float* out = y + (size_t)m * H;
 #pragma unroll
@@ -239,7 +234,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* dy, const floa
         s2 = fmaf(g[i][e], xh[i][e], s2);
       }
     }
-    const float c1 = wave_sum(s1) / (float)H, c2 = wave_sum(s2) / (float)H;
+    const float c1 = wsum(s1) / (float)H, c2 = wsum(s2) / (float)H;
     f32x4* out = reinterpret_cast<f32x4*>(dx + (size_t)m * H);
 #pragma unroll
     for (int i = 0; i < NV4; ++i) {
@@ -726,7 +721,7 @@ __global__ __launch_bounds__(256) void lf_train_fwd_kernel(const float* __restri
   for (int64_t j = c0 + wave; j < c1; j += 4) {
     float a = 0.f;
     for (int c = lane; c < D; c += 64) a = fmaf(us[c], cand[(size_t)j * D + c], a);
-    a = wave_sum(a);
+    a = wsum(a);
     if (lane == 0) scores[j] = a;
   }
 }
@@ -784,7 +779,7 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float* __restrict
   const int64_t pad = mode == 1 ? c_max - (c1 - c0) : 0;
   float mx = pad > 0 ? 0.f : -INFINITY;
   for (int64_t j = c0 + lane; j < c1; j += 64) mx = fmaxf(mx, scores[j] * inv_t);
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wmax(mx);
   float se = 0.f, sp = 0.f, np = 0.f;
   for (int64_t j = c0 + lane; j < c1; j += 64) {
     const float v = scores[j] * inv_t - mx;
@@ -847,7 +842,7 @@ __global__ __launch_bounds__(256) void a_sim_kernel(const float* __restrict__ em
   for (int64_t j = wave; j < N; j += 4) {
     float a = 0.f;
     for (int c = lane; c < D; c += 64) a = fmaf(emb[i * D + c], emb[j * D + c], a);
-    a = wave_sum(a);
+    a = wsum(a);
     if (lane == 0) mat[i * N + j] = a * inv_t;
   }
 }
@@ -865,11 +860,11 @@ __global__ __launch_bounds__(256) void a_loss_kernel(float* __restrict__ mat, co
   // comes out first, so the sum never underflows to 0 however far the diagonal sits above the rest.
   float mx = -INFINITY;
   for (int64_t j = lane; j < N; j += 64) mx = fmaxf(mx, row[j]);
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wmax(mx);
   float m2 = -INFINITY;
   for (int64_t j = lane; j < N; j += 64)
     if (j != i) m2 = fmaxf(m2, row[j] - mx);
-  for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
+  m2 = wmax(m2);
   float se = 0.f, sp = 0.f, np = 0.f, nn = 0.f;
   for (int64_t j = lane; j < N; j += 64) {
     if (j == i) continue;
@@ -877,7 +872,7 @@ __global__ __launch_bounds__(256) void a_loss_kernel(float* __restrict__ mat, co
     se += expf(v - m2);
     if (labels[j] == li) { sp += v; np += 1.f; } else nn += 1.f;
   }
-  se = wave_sum(se); sp = wave_sum(sp); np = wave_sum(np); nn = wave_sum(nn);
+  se = wsum(se); sp = wsum(sp); np = wsum(np); nn = wsum(nn);
   const float lse = N > 1 ? m2 + logf(se) : 0.f;
   if (lane == 0) {
     losses[i] = -(sp - np * lse) / (np + tiny);

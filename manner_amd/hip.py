@@ -1114,27 +1114,47 @@ def adv_loss(rows: Tensor, n_hist: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: 
     return _adv_forward(rows, n_hist, w1, b1, w2, b2, cls, hidden, None)
 
 
-def axis0_attention_any(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
-    """The attention core of ``mha_axis0_any`` on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]; ``stats`` f32 [L0 * B1 * heads * 3]
-    receives the softmax statistics the backward reads."""
+AXIS0_WIDE_MIN_DH = 65      # head dims 65 .. 128 are axis0_attention_wide's; 1 .. 64 are axis0_attention_any's
+
+
+def axis0_family(dh: int) -> str:
+    """The run-time-head-dim family that serves head dim ``dh``: "wide" (csrc/mins.hip) from ``AXIS0_WIDE_MIN_DH`` on, else "any"
+    (csrc/caum.hip).  The seven fixed head dims of ``mha_axis0`` are a third family with entries of its own (csrc/axis0.hip)."""
+    return "wide" if dh >= AXIS0_WIDE_MIN_DH else "any"
+
+
+def _axis0_attention(family: str, qkv: Tensor, heads: int, stats: Optional[Tensor]) -> Tensor:
+    """manner_hip_axis0_attention_<family> on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]."""
     qkv = _dev(qkv, torch.float32, "qkv").contiguous()
     l0, b1, e3 = qkv.shape
     out = torch.empty((l0, b1, e3 // 3), dtype=torch.float32, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        _lib.check(_lib.load().manner_hip_axis0_attention_any(_ptr(qkv), l0, b1, e3 // 3, int(heads), _ptr(out), _ptr(stats), _stream()))
+        _lib.check(getattr(_lib.load(), "manner_hip_axis0_attention_" + family)(_ptr(qkv), l0, b1, e3 // 3, int(heads), _ptr(out), _ptr(stats),
+                                                                               _stream()))
     return out
 
 
-def mha_axis0_any(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
-    """``mha_axis0`` at ANY head dim 1..64 (CAUM ships 25 in its user encoder and 5 in its entity encoder): attention along AXIS 0 of
-    x [L0, B1, E], unmasked.  At L0 < 256 a workgroup takes several (slot, head) pairs, one thread per (pair, row)."""
+def _mha_axis0(family: str, x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    """in-projection, the attention core of ``family``, out-projection."""
     x = _dev(x, torch.float32, "x").contiguous()
     l0, b1, e = x.shape
     if x.numel() == 0:
         return torch.empty_like(x)
     qkv = linear(x.reshape(l0 * b1, e), in_proj_w, in_proj_b).reshape(l0, b1, 3 * e)
-    att = axis0_attention_any(qkv, heads)
+    att = _axis0_attention(family, qkv, heads, None)
     return linear(att.reshape(l0 * b1, e), out_proj_w, out_proj_b).reshape(l0, b1, e)
+
+
+def axis0_attention_any(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
+    """The attention core of ``mha_axis0_any`` on projected rows: qkv [L0, B1, 3E] -> [L0, B1, E]; ``stats`` f32 [L0 * B1 * heads * 3]
+    receives the softmax statistics the backward reads."""
+    return _axis0_attention("any", qkv, heads, stats)
+
+
+def mha_axis0_any(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    """``mha_axis0`` at ANY head dim 1..64 (CAUM ships 25 in its user encoder and 5 in its entity encoder): attention along AXIS 0 of
+    x [L0, B1, E], unmasked.  At L0 < 256 a workgroup takes several (slot, head) pairs, one thread per (pair, row)."""
+    return _mha_axis0("any", x, in_proj_w, in_proj_b, out_proj_w, out_proj_b, heads)
 
 
 CAUM_PARAMS = ("linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "multihead_attention.in_proj_weight",
@@ -1354,7 +1374,6 @@ def lstur_user(user: Tensor, x: Tensor, lengths: Tensor, params: Sequence[Tensor
 
 MINS_PARAMS = ("multihead_attention.in_proj_weight", "multihead_attention.in_proj_bias", "multihead_attention.out_proj.weight",
                "multihead_attention.out_proj.bias") + tuple("gru." + n for n in GRU_PARAMS)
-AXIS0_WIDE_MIN_DH = 65      # head dims 65 .. 128 are axis0_attention_wide's; 1 .. 64 are axis0_attention_any's
 
 
 def _channel_gru_operands(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, channels: int):
@@ -1410,23 +1429,12 @@ def channel_gru_last_hidden(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tens
 def axis0_attention_wide(qkv: Tensor, heads: int, stats: Optional[Tensor] = None) -> Tensor:
     """``axis0_attention_any`` at head dims 65 .. 128 (MINS ships 768 / 6 = 128): qkv [L0, B1, 3E] -> [L0, B1, E]; a wave per query
     row, the lanes along the head dim.  ``stats`` f32 [L0 * B1 * heads * 3] receives the softmax statistics the backward reads."""
-    qkv = _dev(qkv, torch.float32, "qkv").contiguous()
-    l0, b1, e3 = qkv.shape
-    out = torch.empty((l0, b1, e3 // 3), dtype=torch.float32, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _lib.check(_lib.load().manner_hip_axis0_attention_wide(_ptr(qkv), l0, b1, e3 // 3, int(heads), _ptr(out), _ptr(stats), _stream()))
-    return out
+    return _axis0_attention("wide", qkv, heads, stats)
 
 
 def mha_axis0_wide(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
     """``mha_axis0_any`` at head dims 65 .. 128: attention along AXIS 0 of x [L0, B1, E], unmasked."""
-    x = _dev(x, torch.float32, "x").contiguous()
-    l0, b1, e = x.shape
-    if x.numel() == 0:
-        return torch.empty_like(x)
-    qkv = linear(x.reshape(l0 * b1, e), in_proj_w, in_proj_b).reshape(l0, b1, 3 * e)
-    att = axis0_attention_wide(qkv, heads)
-    return linear(att.reshape(l0 * b1, e), out_proj_w, out_proj_b).reshape(l0, b1, e)
+    return _mha_axis0("wide", x, in_proj_w, in_proj_b, out_proj_w, out_proj_b, heads)
 
 
 def mins_check_widths(d: int, f: int, c: int) -> None:
@@ -1456,8 +1464,8 @@ def mins_user(x: Tensor, lengths: Tensor, params: Sequence[Tensor], channels: in
     history slot, unmasked, as in the reference; head dims 65 .. 128 take ``mha_axis0_wide``, 1 .. 64 ``mha_axis0_any``.  The final
     additive pooler over a sequence of one slot is the identity and is not run."""
     x, c = _mins_operands(x, params, channels)
-    mha = mha_axis0_wide if x.shape[2] // c >= AXIS0_WIDE_MIN_DH else mha_axis0_any
-    return channel_gru_last_hidden(mha(x, *params[:4], c), lengths, *params[4:], c)
+    mixed = _mha_axis0(axis0_family(x.shape[2] // c), x, *params[:4], c)
+    return channel_gru_last_hidden(mixed, lengths, *params[4:], c)
 
 
 class HalfTable:

@@ -919,14 +919,17 @@ def mha_axis0(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tenso
     return linear(_Axis0Attention.apply(qkv.contiguous(), int(heads)), out_proj_w, out_proj_b)
 
 
-class _Axis0AttentionAny(torch.autograd.Function):
+class _Axis0AttentionFamily(torch.autograd.Function):
+    """The attention core of a run-time-head-dim family, ``hip.axis0_family``'s "any" or "wide": the forward keeps its output and the
+    softmax statistics, the backward is the family's two entries."""
+
     @staticmethod
-    def forward(ctx, qkv: Tensor, heads: int):
+    def forward(ctx, qkv: Tensor, heads: int, family: str):
         l0, b1, _ = qkv.shape
         stats = torch.empty(l0 * b1 * heads * 3, dtype=torch.float32, device=qkv.device)
-        out = hip.axis0_attention_any(qkv, heads, stats)
+        out = hip._axis0_attention(family, qkv, heads, stats)
         ctx.save_for_backward(qkv, out, stats)
-        ctx.heads = heads
+        ctx.heads, ctx.family = heads, family
         return out
 
     @staticmethod
@@ -937,17 +940,22 @@ class _Axis0AttentionAny(torch.autograd.Function):
         lib = _lib.load()
         with torch.cuda.device(qkv.device):
             g = _f32(g, "grad")
-            _lib.check(lib.manner_hip_axis0_attention_any_backward_q(hip._ptr(qkv), hip._ptr(out), hip._ptr(g), l0, b1, e3 // 3, ctx.heads,
-                                                                     hip._ptr(dqkv), hip._ptr(stats), hip._stream()))
-            _lib.check(lib.manner_hip_axis0_attention_any_backward_kv(hip._ptr(qkv), hip._ptr(g), hip._ptr(stats), l0, b1, e3 // 3, ctx.heads,
-                                                                      hip._ptr(dqkv), hip._stream()))
-        return dqkv, None
+            entry = "manner_hip_axis0_attention_" + ctx.family
+            _lib.check(getattr(lib, entry + "_backward_q")(hip._ptr(qkv), hip._ptr(out), hip._ptr(g), l0, b1, e3 // 3, ctx.heads, hip._ptr(dqkv),
+                                                           hip._ptr(stats), hip._stream()))
+            _lib.check(getattr(lib, entry + "_backward_kv")(hip._ptr(qkv), hip._ptr(g), hip._ptr(stats), l0, b1, e3 // 3, ctx.heads, hip._ptr(dqkv),
+                                                            hip._stream()))
+        return dqkv, None, None
+
+
+def _mha_axis0(family: str, x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
+    qkv = linear(x, in_proj_w, in_proj_b)
+    return linear(_Axis0AttentionFamily.apply(qkv.contiguous(), int(heads), family), out_proj_w, out_proj_b)
 
 
 def mha_axis0_any(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
     """``mha_axis0`` at ANY head dim 1..64, with autograd (CAUM's entity encoder: head dim 5)."""
-    qkv = linear(x, in_proj_w, in_proj_b)
-    return linear(_Axis0AttentionAny.apply(qkv.contiguous(), int(heads)), out_proj_w, out_proj_b)
+    return _mha_axis0("any", x, in_proj_w, in_proj_b, out_proj_w, out_proj_b, heads)
 
 
 class _CaumUser(torch.autograd.Function):
@@ -1201,35 +1209,9 @@ def channel_gru_last_hidden(x: Tensor, lengths: Tensor, w_ih: Tensor, w_hh: Tens
     return _ChannelGru.apply(x, lengths, dims, *params)
 
 
-class _Axis0AttentionWide(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv: Tensor, heads: int):
-        l0, b1, _ = qkv.shape
-        stats = torch.empty(l0 * b1 * heads * 3, dtype=torch.float32, device=qkv.device)
-        out = hip.axis0_attention_wide(qkv, heads, stats)
-        ctx.save_for_backward(qkv, out, stats)
-        ctx.heads = heads
-        return out
-
-    @staticmethod
-    def backward(ctx, g: Tensor):
-        qkv, out, stats = ctx.saved_tensors
-        l0, b1, e3 = qkv.shape
-        dqkv = torch.empty_like(qkv)
-        lib = _lib.load()
-        with torch.cuda.device(qkv.device):
-            g = _f32(g, "grad")
-            _lib.check(lib.manner_hip_axis0_attention_wide_backward_q(hip._ptr(qkv), hip._ptr(out), hip._ptr(g), l0, b1, e3 // 3, ctx.heads,
-                                                                      hip._ptr(dqkv), hip._ptr(stats), hip._stream()))
-            _lib.check(lib.manner_hip_axis0_attention_wide_backward_kv(hip._ptr(qkv), hip._ptr(g), hip._ptr(stats), l0, b1, e3 // 3, ctx.heads,
-                                                                       hip._ptr(dqkv), hip._stream()))
-        return dqkv, None
-
-
 def mha_axis0_wide(x: Tensor, in_proj_w: Tensor, in_proj_b: Tensor, out_proj_w: Tensor, out_proj_b: Tensor, heads: int) -> Tensor:
     """``mha_axis0_any`` at head dims 65 .. 128, with autograd (MINS's user encoder: head dim 128)."""
-    qkv = linear(x, in_proj_w, in_proj_b)
-    return linear(_Axis0AttentionWide.apply(qkv.contiguous(), int(heads)), out_proj_w, out_proj_b)
+    return _mha_axis0("wide", x, in_proj_w, in_proj_b, out_proj_w, out_proj_b, heads)
 
 
 class _UnitPool(torch.autograd.Function):
@@ -1252,8 +1234,7 @@ def mins_user(x: Tensor, lengths: Tensor, params: Sequence[Tensor], channels: in
     attention reads them on behalf of the other users; only the GRU's own input gradient is zero there.  ``pool``: the parameters of
     the final AdditiveAttention, which runs over one slot and is the identity — they receive exact-zero gradients."""
     x, c = hip._mins_operands(x, params, channels)
-    mha = mha_axis0_wide if x.shape[2] // c >= hip.AXIS0_WIDE_MIN_DH else mha_axis0_any
-    out = channel_gru_last_hidden(mha(x, *params[:4], c), lengths, *params[4:], c)
+    out = channel_gru_last_hidden(_mha_axis0(hip.axis0_family(x.shape[2] // c), x, *params[:4], c), lengths, *params[4:], c)
     return _UnitPool.apply(out, *pool) if pool else out
 
 

@@ -387,8 +387,8 @@ def mha_axis0(x: Tensor, in_w: Tensor, in_b: Tensor, out_w: Tensor, out_b: Tenso
 
 AXIS0_DH = (4, 8, 10, 16, 32, 48, 64)
 AXIS0_L0 = (1, 33, 65, 129, 257, 300)
-AXIS0_KEY_TILE_TRAIN = {4: 256, 8: 256, 10: 256, 16: 128, 32: 64, 48: 32, 64: 32}        # train_small.hip
-AXIS0_KEY_TILE_ENTITY = {4: 256, 8: 256, 10: 256, 16: 256, 32: 64, 48: 64, 64: 64}       # entity.hip
+AXIS0_KEY_TILE_TRAIN = {4: 256, 8: 256, 10: 256, 16: 128, 32: 64, 48: 32, 64: 32}        # axis0.hip, training column
+AXIS0_KEY_TILE_ENTITY = {4: 256, 8: 256, 10: 256, 16: 256, 32: 64, 48: 64, 64: 64}       # axis0.hip, inference column
 AXIS0_GEMM_ROUTE = ((12, 3), (129, 3))            # E = 128: L0 * B1 = 36 and 387 rows, below and above one 128-row panel
 
 

@@ -249,7 +249,7 @@ def test_user_encoder_mirror_matches_the_reference(mins_golden, tag, measured):
     for name in MR.POOL_PARAMS:                                  # zero tensors, not None
         assert named[MR.STATE_KEYS[name]].grad is not None and not got["d_" + name].any(), name
     params = [t.detach() for t in enc._params()]
-    mha = hip.mha_axis0_wide if v["D"] // v["C"] > 64 else hip.mha_axis0_any
+    mha = getattr(hip, "mha_axis0_" + hip.axis0_family(v["D"] // v["C"]))
     hidden = hip.channel_gru_last_hidden(mha(x.detach(), *params[:4], v["C"]), lengths, *params[4:], v["C"])
     assert torch.equal(out.detach(), hidden)                    # the output IS the concatenated hidden states
     with torch.no_grad():

@@ -1,7 +1,7 @@
 """The f32 side operators against the float64 restatements of tests/side_ops_ref.py, at the smallest shapes that take every
 kernel loop a second time and fire every guard: the training scorer and loss (train.hip), nn.Linear forward and backward with its
 passes over O and its 128 KiB of LDS, the pooler backward up to its S bound, every head dim of the axis-0 attention dispatch in
-both files across their key tiles and the 256-row block, the embedding and the flat dropout past its grid cap.
+both columns of its key tiles and the 256-row block, the embedding and the flat dropout past its grid cap.
 
 Pure sums of products are held to the DERIVED bar, everything with exp / tanh / log inside to the MEASURED bar (8 x the error of
 the float32 CPU evaluation of the same restatement); both come from the reference side only.  Every test prints its errors next
@@ -140,7 +140,7 @@ def _hip_mha(case):
 @pytest.mark.parametrize("l0", R.AXIS0_L0)
 @pytest.mark.parametrize("dh", R.AXIS0_DH)
 def test_axis0_attention_every_head_dim_forward_and_backward(dh, l0, measured):
-    """train_small.hip's axis0_fwd / bwd_q / bwd_kv at every case of the dispatch: rows below, at and past each key tile and past
+    """axis0.hip's axis0_fwd / bwd_q / bwd_kv at every case of the dispatch: rows below, at and past each key tile and past
     the 256-row block, with the two Linear projections around them"""
     case = R.axis0_case(l0, 3, 2 * dh, 2)
     _hold_measured(case, _run(case, _train_mha), measured)
@@ -149,7 +149,7 @@ def test_axis0_attention_every_head_dim_forward_and_backward(dh, l0, measured):
 @pytest.mark.parametrize("l0", R.AXIS0_L0)
 @pytest.mark.parametrize("dh", R.AXIS0_DH)
 def test_axis0_attention_every_head_dim_inference_kernel(dh, l0, measured):
-    """entity.hip's entity_attn_kernel (other key tiles than the training kernels) through hip.mha_axis0"""
+    """axis0.hip's axis0_fwd_kernel on the inference key tiles (other than the training ones at head dims 16, 48, 64) through hip.mha_axis0"""
     case = R.axis0_case(l0, 3, 2 * dh, 2)
     _hold_measured(case, _hip_mha(case), measured, keys=("out",))
 

@@ -193,7 +193,7 @@ def test_conditions_the_gpu_cases_rely_on():
                     assert per[-1] == 0 and float(case.ref()["loss"]) > 0
                 if kind != "class_of_one" or n == 2:
                     assert float(case.ref()["loss"]) == 0         # no positive pair or no negative pair: the documented zero
-    for dh in R.AXIS0_DH:                                         # every key tile of both files is crossed, and the 256-row block
+    for dh in R.AXIS0_DH:                                         # every key tile of both columns is crossed, and the 256-row block
         for tiles in (R.AXIS0_KEY_TILE_TRAIN, R.AXIS0_KEY_TILE_ENTITY):
             assert any(l > tiles[dh] and l % tiles[dh] for l in R.AXIS0_L0)
     assert max(R.AXIS0_L0) > 256 and R.DROPOUT_N > 8192 * 256
