@@ -992,6 +992,28 @@ int manner_hip_prefix_gather(const int32_t* rows, const int32_t* state, int64_t 
                              const int32_t* row_len, const int32_t* row_src, const float* fresh, int64_t n_fresh,
                              const int32_t* src_of, float* out, manner_hip_stream_t stream);
 
+/* ---- the sentiment annotator's classifier (csrc/seqcls.hip; f32, inference only; an additive export) --------------------------------
+ * manner_hip_seqcls_head is the head of a *ForSequenceClassification checkpoint and the labelling rule of the reference's
+ * SentimentAnnotator.forward (manner/data/components/sentiment_annotator.py:25-38) over the [CLS] rows x [N, H] (rows ldx floats apart)
+ * that manner_hip_encode_cls returns.  dense_w [H, H], dense_b [H]; out_w [L, H], out_b [L].  Per row, in f32:
+ *   h = tanh(dense_w x + dense_b),  z = out_w h + out_b,  p = softmax(z) with the row maximum subtracted,
+ *   a = argmax p, the lowest index at a tie (numpy.argmax),
+ *   score = p[a] if a == pos_idx, -p[a] if a == neg_idx, else (1 - p[a]) (p[L-1] - p[0])
+ * pos_idx / neg_idx: the ids the checkpoint's id2label names 'positive' / 'negative', -1 for none.  The last branch reads positions
+ * L - 1 and 0 whatever those labels are named, as the reference does.  A row with a non-finite logit gets label -1, score NaN and NaN
+ * probabilities.  probs [N, L] (may be NULL: not written), label int32 [N], score [N].
+ * One launch: a workgroup owns a panel of rows (32 below 8192 rows, else 128) and walks all column tiles of the dense layer for it on
+ * the f32 matrix cores; tanh and the out-projection are each tile's epilogue, and softmax, argmax and the rule finish in the same
+ * workgroup.  The [N, H] hidden activation is never written; there is no workspace and no atomic.  A hidden feature is one k-ascending
+ * fmaf chain, a logit one fmaf chain over the hidden features in ascending order starting from out_b: the bits of a row do not depend
+ * on N, on the panel or on the row's place in the call.
+ * 1 <= L <= 64; H a multiple of 4, H <= 1024; 0 <= N < 2^31 (N == 0 launches nothing and returns OK); ldx >= H; pos_idx, neg_idx in
+ * [-1, L).  Anything else, or a null pointer other than probs (x, label and score may be NULL at N == 0), is MANNER_HIP_E_INVALID with a message that names the entry, before any
+ * launch. */
+int manner_hip_seqcls_head(const float* x, int64_t ldx, const float* dense_w, const float* dense_b, const float* out_w, const float* out_b,
+                           int64_t N, int32_t H, int32_t L, int32_t pos_idx, int32_t neg_idx, float* probs, int32_t* label, float* score,
+                           manner_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

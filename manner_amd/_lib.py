@@ -195,6 +195,7 @@ SIGNATURES = {
     "manner_hip_adv_loss_backward_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "manner_hip_adv_loss": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
     "manner_hip_adv_loss_backward": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "manner_hip_seqcls_head": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None

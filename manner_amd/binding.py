@@ -78,6 +78,12 @@ discriminator with its wrapped one-hot target — are built as ``hotpath.senti_d
 and ``hotpath.senti_debias_discriminator_step`` (csrc/debias.hip) for a ``Generator.forward`` / ``training_step`` that delegates to
 them; ``toggle_optimizer``, the two optimisers, the logging and the metrics stay the reference's.
 
+``install(annotator=True)`` (a keyword of its own, default off) rebinds the data pipeline's ``SentimentAnnotator`` (reference
+manner/data/components/sentiment_annotator.py) to ``manner_amd.data.components.sentiment_annotator.SentimentAnnotator`` in the three
+modules that hold the name: ``manner.data.components.sentiment_annotator`` and ``mind_dataframe`` / ``adressa_dataframe``, which import
+the class by name.  The mirror has no hub access: the frames' ``SentimentAnnotator(name, max_length)`` call then needs ``name`` to be
+a local HF directory.  Nothing else of ``manner.data`` is touched.
+
 Use (no reference source line changes):
 
     python -m manner_amd.run manner/train.py experiment=cr_module_mind_title_scl_lf      # = install() + runpy of the script
@@ -110,6 +116,8 @@ BASELINE_TARGETS = {
 _REF_PKG = "manner.models.components"
 _MIRROR_PKG = "manner_amd.models.components"
 _installed: Dict[str, Dict[str, type]] = {}          # module name -> {class name: the reference's original class}
+ANNOTATOR_MODULES = ("manner.data.components.sentiment_annotator", "manner.data.components.mind_dataframe",
+                     "manner.data.components.adressa_dataframe")
 
 
 def _targets(baselines: Sequence[str]) -> Dict[str, Tuple[str, ...]]:
@@ -125,13 +133,25 @@ def _targets(baselines: Sequence[str]) -> Dict[str, Tuple[str, ...]]:
     return targets
 
 
-def install(reference_root: Optional[str] = None, baselines: Sequence[str] = ()) -> Dict[str, List[str]]:
+def _install_annotator(report: Dict[str, List[str]]) -> None:
+    from .data.components.sentiment_annotator import SentimentAnnotator as mirror
+    for name in ANNOTATOR_MODULES:
+        mod = importlib.import_module(name)
+        cur = getattr(mod, "SentimentAnnotator")
+        if cur is mirror:
+            continue
+        _installed.setdefault(name, {}).setdefault("SentimentAnnotator", cur)
+        setattr(mod, "SentimentAnnotator", mirror)
+        report.setdefault(name, []).append("SentimentAnnotator")
+
+
+def install(reference_root: Optional[str] = None, baselines: Sequence[str] = (), annotator: bool = False) -> Dict[str, List[str]]:
     """Rebind the mirrored classes inside the reference's ``manner.models.components`` modules.  ``reference_root``: a checkout
     of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  ``baselines``: opt-in sets of further classes
     (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention; ``"caum_plm"``: CAUMCategoryEncoder, CAUMNewsEncoder,
     CAUMUserEncoder, DenseAttention; ``"lstur_plm"``: LSTURCategoryEncoder, LSTURNewsEncoder, LSTURUserEncoder; ``"mins_plm"``:
     NAMLCategoryEncoder, NAMLNewsEncoder, MINSUserEncoder; ``"naml_plm"``: NAMLCategoryEncoder, NAMLNewsEncoder); an unknown name raises
-    ValueError.  Returns {module: [rebound
+    ValueError.  ``annotator``: also rebind ``SentimentAnnotator`` in the reference's data components (off by default).  Returns {module: [rebound
     names]} (also the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
     targets = _targets(baselines)
     if reference_root and reference_root not in sys.path:
@@ -171,6 +191,8 @@ def install(reference_root: Optional[str] = None, baselines: Sequence[str] = ())
                     _installed.setdefault(name, {}).setdefault(attr, val)
                     setattr(mod, attr, swaps[id(val)])
                     report.setdefault(name, []).append(attr)
+    if annotator:
+        _install_annotator(report)
     return report
 
 

@@ -54,6 +54,9 @@ PRESETS = {
     "bert-base-uncased": EncoderConfig(),
     "roberta-base": EncoderConfig(arch=ARCH_ROBERTA, vocab=50265, max_pos=514, type_vocab=1,
                                   ln_eps=1e-5, pad_id=1),
+    # the multilingual RoBERTa of the sentiment annotator's default checkpoint (cardiffnlp/twitter-xlm-roberta-base-sentiment)
+    "xlm-roberta-base": EncoderConfig(arch=ARCH_ROBERTA, vocab=250002, max_pos=514, type_vocab=1,
+                                      ln_eps=1e-5, pad_id=1),
     "roberta-large": EncoderConfig(arch=ARCH_ROBERTA, hidden=1024, layers=24, heads=16,
                                    intermediate=4096, vocab=50265, max_pos=514, type_vocab=1,
                                    ln_eps=1e-5, pad_id=1),
@@ -85,7 +88,11 @@ def from_hf_config(path: str) -> EncoderConfig:
     if os.path.isdir(path):
         path = os.path.join(path, "config.json")
     with open(path) as f:
-        c = json.load(f)
+        return from_hf_dict(json.load(f))
+
+
+def from_hf_dict(c: dict) -> EncoderConfig:
+    """The fields of an HF ``config.json`` (``PretrainedConfig.to_dict()``)."""
     mt = c.get("model_type", "bert")
     if mt == "distilbert":
         if c.get("activation", "gelu") != "gelu":

@@ -1254,6 +1254,34 @@ def linear_tanh(x: Tensor, weight: Tensor, bias: Optional[Tensor]) -> Tensor:
     return y
 
 
+def seqcls_head(x: Tensor, dense_w: Tensor, dense_b: Tensor, out_w: Tensor, out_b: Tensor, pos_idx: int = -1, neg_idx: int = -1,
+                with_probs: bool = True) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """The classifier of a ``*ForSequenceClassification`` checkpoint and the reference annotator's rule (sentiment_annotator.py:25-38) on
+    [CLS] rows, one launch (csrc/seqcls.hip): x [N, H] f32 (a row-strided view is read in place) -> (label int32 [N], score f32 [N],
+    probs f32 [N, L] or None).  tanh(dense) -> out -> softmax -> argmax (lowest index at a tie); score = p[a] / -p[a] for the ids
+    ``pos_idx`` / ``neg_idx`` (-1: none), else (1 - p[a]) (p[L-1] - p[0]).  A row with a non-finite logit: label -1, score NaN."""
+    x = _dev(x, torch.float32, "x")
+    if x.dim() != 2:
+        raise ValueError(f"seqcls_head: x {tuple(x.shape)} must be [N, H]")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    n, h = x.shape
+    ldx = x.stride(0) if n > 1 else h
+    dense_w, dense_b = _dev(dense_w, torch.float32, "dense_w").contiguous(), _dev(dense_b, torch.float32, "dense_b").contiguous()
+    out_w, out_b = _dev(out_w, torch.float32, "out_w").contiguous(), _dev(out_b, torch.float32, "out_b").contiguous()
+    nl = out_w.shape[0]
+    if tuple(dense_w.shape) != (h, h) or tuple(dense_b.shape) != (h,) or tuple(out_w.shape) != (nl, h) or tuple(out_b.shape) != (nl,):
+        raise ValueError(f"seqcls_head: dense {tuple(dense_w.shape)} / {tuple(dense_b.shape)}, out {tuple(out_w.shape)} / {tuple(out_b.shape)} "
+                         f"do not fit x [N, {h}]")
+    label = torch.empty((n,), dtype=torch.int32, device=x.device)
+    score = torch.empty((n,), dtype=torch.float32, device=x.device)
+    probs = torch.empty((n, nl), dtype=torch.float32, device=x.device) if with_probs else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().manner_hip_seqcls_head(_ptr(x), ldx, _ptr(dense_w), _ptr(dense_b), _ptr(out_w), _ptr(out_b), n, h, nl,
+                                                      int(pos_idx), int(neg_idx), _ptr(probs), _ptr(label), _ptr(score), _stream()))
+    return label, score, probs
+
+
 def relu(x: Tensor) -> Tensor:
     x = _dev(x, torch.float32, "x").contiguous()
     out = torch.empty_like(x)

@@ -174,3 +174,43 @@ def make_mha_pool_weights(dim: int, query_dim: int, seed: int = 42, prefix: str 
     for k, v in make_additive_attention_weights(dim, query_dim, seed=seed, prefix=prefix + "additive_attention.").items():
         out[k] = v
     return out
+
+
+_SEQCLS_PREFIXES = ("roberta.", "bert.", "xlm_roberta.")
+
+
+def split_sequence_classifier(state_dict):
+    """A ``*ForSequenceClassification`` state dict -> (plm_weights, head): the encoder's parameters under ``BertModel`` /
+    ``RobertaModel`` names (the ``roberta.`` / ``bert.`` prefix stripped) and the head as ``{"dense.weight", "dense.bias", "out.weight",
+    "out.bias"}``.  RobertaForSequenceClassification (built with ``add_pooling_layer=False``: no pooler keys) classifies
+    ``out_proj(tanh(dense([CLS])))`` — ``classifier.dense.*`` -> dense, ``classifier.out_proj.*`` -> out; BertForSequenceClassification
+    classifies ``classifier(tanh(pooler.dense([CLS])))`` — ``pooler.dense.*`` -> dense, ``classifier.*`` -> out: the same arithmetic
+    (dropout is the identity in eval mode).  DistilBERT's ReLU ``pre_classifier`` is a different head and raises ValueError."""
+    if any(k.startswith("pre_classifier.") for k in state_dict):
+        raise ValueError("split_sequence_classifier: DistilBertForSequenceClassification's ReLU pre_classifier head is not supported "
+                         "(tanh-pooled [CLS] heads only: RoBERTa / XLM-R / BERT)")
+    plm, rest = {}, {}
+    for k, v in state_dict.items():
+        for p in _SEQCLS_PREFIXES:
+            if k.startswith(p):
+                plm[k[len(p):]] = v
+                break
+        else:
+            rest[k] = v
+    if "classifier.dense.weight" in rest:                                         # the RoBERTa layout
+        names = {"dense.weight": "classifier.dense.weight", "dense.bias": "classifier.dense.bias",
+                 "out.weight": "classifier.out_proj.weight", "out.bias": "classifier.out_proj.bias"}
+        src = rest
+    elif "classifier.weight" in rest and "pooler.dense.weight" in plm:            # the BERT layout
+        names = {"dense.weight": "pooler.dense.weight", "dense.bias": "pooler.dense.bias",
+                 "out.weight": "classifier.weight", "out.bias": "classifier.bias"}
+        src = {**plm, **rest}
+    else:
+        raise ValueError("split_sequence_classifier: neither classifier.dense / classifier.out_proj (RoBERTa) nor pooler.dense / classifier "
+                         f"(BERT) found among {sorted(rest)[:8]}")
+    missing = [n for n in names.values() if n not in src]
+    if missing:
+        raise ValueError(f"split_sequence_classifier: the state dict lacks {missing}")
+    head = {k: src[n] for k, n in names.items()}
+    plm = {k: v for k, v in plm.items() if not k.endswith("position_ids")}
+    return plm, head
