@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib", "libmanner_hip.so")
-SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "scoring.hip", "pool.hip", "entity.hip", "metrics.hip", "collate.hip", "cache.hip", "encoder.hip", "train.hip", "train_attn.hip", "wgrad.hip", "train_small.hip", "axis0.hip", "poly.hip", "caum.hip", "gru.hip", "mins.hip", "miner.hip", "aspect.hip", "debias.hip", "seqcls.hip"]
+SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "scoring.hip", "pool.hip", "entity.hip", "metrics.hip", "collate.hip", "cache.hip", "encoder.hip", "train.hip", "train_attn.hip", "wgrad.hip", "train_small.hip", "axis0.hip", "rows_f32.hip", "poly.hip", "caum.hip", "gru.hip", "mins.hip", "miner.hip", "aspect.hip", "debias.hip", "seqcls.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
@@ -30,7 +30,7 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     # the hand-scheduled GEMM K-loops are generated text (tools/gen_gemm_w.py), committed; a checkout without them regenerates
     if not all(os.path.exists(os.path.join(CSRC, f"gemm_w{nw}_asm.inc")) for nw in (8, 4)):
         subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_gemm_w.py")], check=True, capture_output=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "train_common.h"), os.path.join(CSRC, "gemm_w4_asm.inc"), os.path.join(CSRC, "gemm_w8_asm.inc"), os.path.join(ROOT, "include", "manner_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "train_common.h"), os.path.join(CSRC, "row_head.h"), os.path.join(CSRC, "gemm_w4_asm.inc"), os.path.join(CSRC, "gemm_w8_asm.inc"), os.path.join(ROOT, "include", "manner_hip.h")]
     # a library newer than every source and header is current, whether or not the objects it was linked from are still there
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest([os.path.join(CSRC, s) for s in SOURCES] + headers):
         return LIB

@@ -25,15 +25,12 @@ namespace {
 constexpr int CA_MAX_S = 256, CA_MAX_W = 1024, CA_MAX_DH = 64;
 constexpr int CA_BLOCK = 256, CA_WAVE = 64, CA_WAVES = CA_BLOCK / CA_WAVE;      // threads per workgroup, lanes per wave, waves per workgroup
 constexpr int CA_FLAT_GRID = 8192;   // most workgroups of a grid-stride elementwise launch
-constexpr int CA_ALIGN = 64;         // floats every saved / workspace buffer is aligned to
 constexpr int CA_ROWS = 8;       // rows per workgroup of the linear, data-gradient, score and row kernels
 constexpr int CA_OT = 64;        // output features per workgroup of the linear kernel
 constexpr int CA_KS = 128;       // input features per step of the linear kernel (x rows 4 KiB, weight tile CA_OT x (CA_KS + 1) floats = 32 KiB)
 constexpr int CA_OC = 1024;      // output features staged per pass of the data-gradient kernel (32 KiB)
 constexpr int CA_LDS = 7168;     // floats of each of the two staged attention operands (2 x 28 KiB)
 constexpr int CA_KT = 64;        // rows of the other side per tile when a (slot, head) pair does not fit CA_LDS or B > 256
-constexpr int WG_MAX_GROUPS = 16, WG_ROWS = 64;      // weight gradient: row groups, least rows per group (the scheme of poly.hip)
-constexpr int CS_COLS = 64, CS_GROUPS = 16;          // bias gradient: columns per workgroup, row groups (as train_small.hip)
 static_assert(CA_KT * CA_MAX_DH <= CA_LDS, "a tile of the largest head fits");
 static_assert(CA_OT * CA_WAVES == CA_BLOCK && CA_WAVES == 4 && CA_KS % CA_WAVES == 0, "lin_kernel: thread = (output feature, K quarter)");
 static_assert(CA_MAX_S % CA_WAVE == 0, "one wave holds a user's scores, CA_MAX_S / CA_WAVE per lane");
@@ -159,58 +156,6 @@ __global__ __launch_bounds__(CA_BLOCK) void lin_dx_kernel(const float* __restric
       }
   }
 }
-// dW[o, k] = sum_r dy[r, o] x[r, k], dW rows ldo apart.  grid (ceil(K / 256), O, G): group g sums its rows on four chains into
-// part[g][o][k] (straight into dW when G == 1); wgrad_reduce_kernel adds the G partial sums in ascending g.
-__global__ __launch_bounds__(CA_BLOCK) void wgrad_rows_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ x, int64_t R, int K, int O,
-                                                         int64_t chunk, float* __restrict__ out, int ldo, int64_t gstride) {
-  const int k = blockIdx.x * CA_BLOCK + threadIdx.x, o = blockIdx.y;
-  if (k >= K) return;
-  const int64_t r0 = (int64_t)blockIdx.z * chunk, r1 = min(R, r0 + chunk);
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  int64_t r = r0;
-  for (; r + 3 < r1; r += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) a[u] = fmaf(dy[(r + u) * ldy + o], x[(r + u) * K + k], a[u]);
-  }
-  for (; r < r1; ++r) a[0] = fmaf(dy[r * ldy + o], x[r * K + k], a[0]);
-  out[(size_t)blockIdx.z * gstride + (size_t)o * ldo + k] = (a[0] + a[1]) + (a[2] + a[3]);
-}
-__global__ __launch_bounds__(CA_BLOCK) void wgrad_reduce_kernel(const float* __restrict__ part, int K, int O, int G, float* __restrict__ dW, int ldo) {
-  const int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x, n = (int64_t)O * K;
-  if (i >= n) return;
-  float s = part[i];
-  for (int g = 1; g < G; ++g) s += part[(size_t)g * n + i];
-  const int64_t o = i / K;
-  dW[o * ldo + (i - o * K)] = s;
-}
-// db[o] = sum_r dy[r, o] (train_small.hip's colsum_small_kernel with a leading dimension)
-__global__ __launch_bounds__(CS_COLS * CS_GROUPS) void colsum_kernel(const float* __restrict__ dy, int ldy, int64_t R, int O, float* __restrict__ db) {
-  __shared__ float red[CS_GROUPS][CS_COLS];
-  const int col = threadIdx.x % CS_COLS, g = threadIdx.x / CS_COLS;
-  const int o = blockIdx.x * CS_COLS + col;
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  if (o < O) {
-    int64_t r = g;
-    for (; r + 3 * CS_GROUPS < R; r += 4 * CS_GROUPS) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] += dy[(r + u * CS_GROUPS) * ldy + o];
-    }
-    for (; r < R; r += CS_GROUPS) s[0] += dy[r * ldy + o];
-  }
-  red[g][col] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  if (g == 0 && o < O) {
-    float t[CS_GROUPS];
-#pragma unroll
-    for (int i = 0; i < CS_GROUPS; ++i) t[i] = red[i][col];
-#pragma unroll
-    for (int w = CS_GROUPS / 2; w > 0; w >>= 1) {
-#pragma unroll
-      for (int i = 0; i < w; ++i) t[i] += t[i + w];
-    }
-    db[o] = t[0];
-  }
-}
 
 int launch_lin(bool tanh_act, const float* x, const float* W, int ldw, const float* b, const float* rowadd, int S, int64_t R, int K, int O, float* y,
                int ldy, hipStream_t s, float* deriv = nullptr) {
@@ -222,26 +167,6 @@ int launch_lin(bool tanh_act, const float* x, const float* W, int ldw, const flo
 }
 int launch_dx(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, const float* add, const float* mul, float* dx, hipStream_t s) {
   hipLaunchKernelGGL(lin_dx_kernel, dim3((unsigned)((R + CA_ROWS - 1) / CA_ROWS), (unsigned)((K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, dy, ldy, W, ldw, R, K, O, add, mul, dx);
-  MANNER_LAUNCH_CHECK();
-  return MANNER_HIP_OK;
-}
-int wgrad_groups(int64_t R) { return (int)std::max<int64_t>(1, std::min<int64_t>(WG_MAX_GROUPS, R / WG_ROWS)); }
-// R >= 1; part holds wgrad_groups(R) * O * K floats
-int launch_wgrad(const float* dy, int ldy, const float* x, int64_t R, int K, int O, float* part, float* dW, int ldo, hipStream_t s) {
-  const int G = wgrad_groups(R);
-  const int64_t chunk = (R + G - 1) / G;
-  const dim3 g((unsigned)((K + CA_BLOCK - 1) / CA_BLOCK), (unsigned)O, (unsigned)G);
-  if (G == 1) hipLaunchKernelGGL(wgrad_rows_kernel, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, R, K, O, chunk, dW, ldo, (int64_t)0);
-  else hipLaunchKernelGGL(wgrad_rows_kernel, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, R, K, O, chunk, part, K, (int64_t)O * K);
-  MANNER_LAUNCH_CHECK();
-  if (G > 1) {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((int64_t)O * K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, part, K, O, G, dW, ldo);
-    MANNER_LAUNCH_CHECK();
-  }
-  return MANNER_HIP_OK;
-}
-int launch_colsum(const float* dy, int ldy, int64_t R, int O, float* db, hipStream_t s) {
-  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((O + CS_COLS - 1) / CS_COLS)), dim3(CS_COLS * CS_GROUPS), 0, s, dy, ldy, R, O, db);
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }
@@ -643,18 +568,8 @@ int caum_check(const char* who, int64_t B, int64_t S, int D, int F, int U, int H
   m = Dims{B, S, B * S, D, F, U, H1, H2, heads};
   return MANNER_HIP_OK;
 }
-struct Bump {
-  float* base;
-  size_t off = 0;
-  explicit Bump(void* p) : base(static_cast<float*>(p)) {}
-  float* take(size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + CA_ALIGN - 1) / CA_ALIGN * CA_ALIGN;
-    return p;
-  }
-};
 struct Saved { float *a1, *a2, *cd, *cat, *h2, *qkv, *att, *stats, *all, *ct, *t1, *t2, *d1, *d2, *score, *g; };
-void plan_saved(Bump& b, Saved& s, const Dims& m) {
+void plan_saved(FloatBump& b, Saved& s, const Dims& m) {
   const size_t R = (size_t)m.R, B = (size_t)m.B;
   s.a1 = b.take(R * 4 * m.D);
   s.a2 = b.take(R * 2 * m.D);
@@ -675,7 +590,7 @@ void plan_saved(Bump& b, Saved& s, const Dims& m) {
 }
 struct Work { float *ds, *wq, *dt2, *dt1, *dall, *dct, *dcd, *dcat, *datt, *dqkv, *dh2, *da2, *da1, *part; };
 // everything but the partial sums of the weight gradients
-void plan_work_rows(Bump& b, Work& w, const Dims& m) {
+void plan_work_rows(FloatBump& b, Work& w, const Dims& m) {
   const size_t R = (size_t)m.R, B = (size_t)m.B;
   w.ds = b.take(R);
   w.wq = b.take(R);
@@ -691,11 +606,11 @@ void plan_work_rows(Bump& b, Work& w, const Dims& m) {
   w.da2 = b.take(R * 2 * m.D);
   w.da1 = b.take(R * 4 * m.D);
 }
-void plan_work(Bump& b, Work& w, const Dims& m) {
+void plan_work(FloatBump& b, Work& w, const Dims& m) {
   plan_work_rows(b, w, m);
   const size_t ok = std::max({(size_t)m.F * 4 * m.D, (size_t)m.U * 2 * m.D, (size_t)3 * m.U * m.U, (size_t)m.U * (m.F + m.U), (size_t)m.H1 * m.U,
                               (size_t)m.H2 * m.H1, (size_t)m.H2});
-  w.part = b.take((size_t)wgrad_groups(m.R) * ok);
+  w.part = b.take((size_t)wgrad_rows_groups(m.R) * ok);
 }
 
 // ---------------------------------------------------------------- all candidates of a call on shared history products
@@ -910,7 +825,7 @@ __global__ __launch_bounds__(CA_BLOCK) void window_kernel(const float* __restric
   }
 }
 // out[k, j] = in[j, k], in [n, n] (out_proj.weight, for the fold W3[:, F:] Wout as a row-times-row product)
-__global__ __launch_bounds__(CA_BLOCK) void transpose_kernel(const float* __restrict__ in, int n, float* __restrict__ out) {
+__global__ __launch_bounds__(CA_BLOCK) void transpose_square_kernel(const float* __restrict__ in, int n, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * CA_BLOCK + threadIdx.x;
   if (i >= (int64_t)n * n) return;
   const int k = (int)(i / n), j = (int)(i - (int64_t)k * n);
@@ -931,7 +846,7 @@ struct AllBufs {
   float *win, *wx, *hx, *qh, *a, *cx1, *cx2, *qc, *bcand, *ct, *owt, *fold, *ba;      // once per call
   float *att, *all, *t1, *t2, *score, *g, *cd, *outp;                                    // per pass of cp columns
 };
-void plan_all(Bump& b, AllBufs& w, const Dims& m, int64_t C, int64_t cp) {
+void plan_all(FloatBump& b, AllBufs& w, const Dims& m, int64_t C, int64_t cp) {
   const size_t R = (size_t)m.R, N = (size_t)m.B * C, P = (size_t)m.B * cp, W = P * m.S;
   w.win = b.take(R * 3 * m.D);
   w.wx = b.take(R * m.F);
@@ -956,7 +871,7 @@ void plan_all(Bump& b, AllBufs& w, const Dims& m, int64_t C, int64_t cp) {
   w.outp = b.take(P);
 }
 size_t all_bytes(const Dims& m, int64_t C, int64_t cp) {
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   AllBufs w;
   plan_all(b, w, m, C, cp);
   return b.off * sizeof(float) + 256;
@@ -977,7 +892,7 @@ int caum_all_check(const char* who, int64_t B, int64_t S, int64_t C, int D, int 
 
 // ---------------------------------------------------------------- training over all candidate columns
 // The per-column training entry with the C columns as rows: R' = B C S rows in (b, c, s) order, (b, c) a pseudo-user of S slots, so
-// that score_kernel, user_kernel, tail_rows_kernel, segsum_kernel and colsum_kernel run as they are and the attention sees
+// that score_kernel, user_kernel, tail_rows_kernel, segsum_kernel and colsum_rows_kernel run as they are and the attention sees
 // qkv [B, C S, 3U].  Nothing is shared between the columns — the reference draws a fresh dropout2 mask of the clicked news per column —
 // but every product runs once over C times the rows, on the matrix cores: wlin_kernel forward and for the data gradients (over a weight
 // transposed once per call), mwgrad_kernel for the weight gradients.  Column c draws with seeds[c] at the element indices of the
@@ -1047,17 +962,6 @@ __global__ __launch_bounds__(CA_BLOCK) void cand_dx_cols_kernel(const float* __r
     if (s & 1) a1 += v; else a0 += v;
   }
   out[(size_t)pu * D + j] = col_drop(d1, seeds, c).apply((a0 + a1) + dcd[(size_t)pu * D + j], (uint64_t)b * D + j);
-}
-// out[k, o] = in[o, k]: in [O, K] rows ldw apart (a column range of a weight), out [K, O] contiguous — the operand of a data gradient
-// dx = dy W as wlin_kernel's row-times-row product.  grid (ceil(K / 32), ceil(O / 32)), a 32 x 32 tile through LDS, both sides coalesced.
-__global__ __launch_bounds__(CA_BLOCK) void transpose_ld_kernel(const float* __restrict__ in, int ldw, int O, int K, float* __restrict__ out) {
-  __shared__ float t[32][33];
-  const int k0 = blockIdx.x * 32, o0 = blockIdx.y * 32, tx = threadIdx.x % 32, ty = threadIdx.x / 32;
-  for (int i = ty; i < 32; i += CA_BLOCK / 32)
-    t[i][tx] = (o0 + i < O && k0 + tx < K) ? in[(size_t)(o0 + i) * ldw + k0 + tx] : 0.f;
-  __syncthreads();
-  for (int i = ty; i < 32; i += CA_BLOCK / 32)
-    if (k0 + i < K && o0 + tx < O) out[(size_t)(k0 + i) * O + o0 + tx] = t[tx][i];
 }
 
 // dW[o, k] = sum_r dy[r, o] x[r, k] on the matrix cores, true f32: the product dy^T x with the ROWS as the contraction axis.  dy rows
@@ -1173,27 +1077,23 @@ int launch_mwgrad(const float* dy, int ldy, const float* x, int ldx, int64_t R, 
   if (p.small) hipLaunchKernelGGL(mwgrad_kernel<true>, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, ldx, R, K, O, p.chunk, out, ld, gs);
   else hipLaunchKernelGGL(mwgrad_kernel<false>, g, dim3(CA_BLOCK), 0, s, dy, ldy, x, ldx, R, K, O, p.chunk, out, ld, gs);
   MANNER_LAUNCH_CHECK();
-  if (p.G > 1) {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((int64_t)O * K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, part, K, O, p.G, dW, ldo);
-    MANNER_LAUNCH_CHECK();
-  }
-  return MANNER_HIP_OK;
+  return p.G > 1 ? launch_wgrad_reduce(part, K, O, p.G, dW, ldo, s) : MANNER_HIP_OK;
 }
 // the weight gradients of the all-columns backward, selected per launch by the row count alone: at equal (R, K, O) of the shipped widths
 // (profiles/caum/kernel_trace.json, weight_gradient_equal_shapes) mwgrad_kernel is 2.1 - 7.7 x wgrad_rows_kernel from 320 rows on and
 // slower only at the 40 rows of the B C pairs at B = 8 (7.3 against 5.6 us: one staging, 28 workgroups) — below MW_MIN_ROWS rows the
 // one-thread-per-(o, k) kernel runs, in one group (wgrad_groups: no partial sums).  x [R, K] contiguous.
 constexpr int MW_MIN_ROWS = 64;
-static_assert(MW_MIN_ROWS <= WG_ROWS, "below MW_MIN_ROWS rows wgrad_rows_kernel writes dW itself");
+static_assert(MW_MIN_ROWS <= WGRAD_GROUP_ROWS, "below MW_MIN_ROWS rows wgrad_rows_kernel writes dW itself");
 int launch_wgrad_all(const float* dy, int ldy, const float* x, int64_t R, int K, int O, float* part, float* dW, int ldo, hipStream_t s) {
-  if (R < MW_MIN_ROWS) return launch_wgrad(dy, ldy, x, R, K, O, nullptr, dW, ldo, s);
+  if (R < MW_MIN_ROWS) return launch_wgrad_rows(dy, ldy, x, R, K, O, nullptr, dW, ldo, s);
   return launch_mwgrad(dy, ldy, x, K, R, K, O, part, dW, ldo, s);
 }
 // dx [R, K] = (add + dy W) * mul on wlin_kernel: W [O, K] (rows ldw apart) transposed into wt [K, O] first
 int launch_mdx(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, const float* add, const float* mul, float* dx, float* wt,
                hipStream_t s) {
-  hipLaunchKernelGGL(transpose_ld_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)((O + 31) / 32)), dim3(CA_BLOCK), 0, s, W, ldw, O, K, wt);
-  MANNER_LAUNCH_CHECK();
+  const int rc = launch_transpose_tile(W, ldw, O, K, wt, s);
+  if (rc) return rc;
   return launch_wlin(false, dy, ldy, wt, O, nullptr, nullptr, nullptr, RowMap{1, 1, 1, 0}, R, O, K, dx, K, s, nullptr, add, mul);
 }
 
@@ -1208,7 +1108,7 @@ int caum_train_all_check(const char* who, int64_t B, int64_t S, int64_t C, int D
   return MANNER_HIP_OK;
 }
 struct WorkAll { Work w; float *dall2, *dcd2, *wt, *mpart; };
-void plan_work_all(Bump& b, WorkAll& a, const Dims& m) {
+void plan_work_all(FloatBump& b, WorkAll& a, const Dims& m) {
   const size_t R = (size_t)m.R, P = (size_t)m.B;
   plan_work_rows(b, a.w, m);
   a.w.part = nullptr;
@@ -1300,7 +1200,7 @@ int manner_hip_axis0_attention_any_backward_kv(const float* qkv, const float* gr
 size_t manner_hip_caum_user_saved_bytes(int64_t B, int64_t S, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads) {
   if (B <= 0 || S <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
   const Dims m{B, S, B * S, D, F, U, H1, H2, heads};
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Saved s;
   plan_saved(b, s, m);
   return b.off * sizeof(float) + 256;
@@ -1320,7 +1220,7 @@ int manner_hip_caum_user_forward(const float* x, const float* c, int64_t c_strid
   if (c_stride < D) return fail(MANNER_HIP_E_INVALID, "caum_user: candidate row stride %lld < D=%d", (long long)c_stride, D);
   if (saved_bytes < manner_hip_caum_user_saved_bytes(B, S, D, F, U, H1, H2, heads)) return fail(MANNER_HIP_E_WORKSPACE, "caum_user: saved buffer too small");
   hipStream_t s = (hipStream_t)stream;
-  Bump bump(saved);
+  FloatBump bump(saved);
   Saved sv;
   plan_saved(bump, sv, m);
   const int64_t R = m.R;
@@ -1355,7 +1255,7 @@ int manner_hip_caum_user_forward(const float* x, const float* c, int64_t c_strid
 size_t manner_hip_caum_user_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads) {
   if (B <= 0 || S <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
   const Dims m{B, S, B * S, D, F, U, H1, H2, heads};
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Work w;
   plan_work(b, w, m);
   return b.off * sizeof(float) + 256;
@@ -1384,7 +1284,7 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
   if (saved_bytes < manner_hip_caum_user_saved_bytes(B, S, D, F, U, H1, H2, heads)) return fail(MANNER_HIP_E_WORKSPACE, "caum_user_backward: saved buffer too small");
   if (workspace_bytes < manner_hip_caum_user_backward_workspace_bytes(B, S, D, F, U, H1, H2, heads))
     return fail(MANNER_HIP_E_WORKSPACE, "caum_user_backward: workspace too small");
-  Bump bs(saved), bw(workspace);
+  FloatBump bs(saved), bw(workspace);
   Saved sv;
   Work w;
   plan_saved(bs, sv, m);
@@ -1399,50 +1299,50 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
   hipLaunchKernelGGL(tail_rows_kernel, dim3(row_tiles), dim3(CA_BLOCK), 0, s, w.ds, w.wq, params[P_WC], sv.d2, sv.cd, R, Si, H2, U, w.dt2, w.dall);
   MANNER_LAUNCH_CHECK();
   // dense_att.linear3: d wc = sum_r ds[r] t2[r]; d bc is zero in exact arithmetic (the softmax is shift-invariant)
-  if ((rc = launch_wgrad(w.ds, 1, sv.t2, R, H2, 1, w.part, grads[P_WC], H2, s))) return rc;
+  if ((rc = launch_wgrad_rows(w.ds, 1, sv.t2, R, H2, 1, w.part, grads[P_WC], H2, s))) return rc;
   MANNER_HIP_TRY(hipMemsetAsync(grads[P_BC], 0, sizeof(float), s));
   // dense_att.linear2
-  if ((rc = launch_wgrad(w.dt2, H2, sv.t1, R, H1, H2, w.part, grads[P_WB], H1, s))) return rc;
-  if ((rc = launch_colsum(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dt2, H2, sv.t1, R, H1, H2, w.part, grads[P_WB], H1, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
   if ((rc = launch_dx(w.dt2, H2, params[P_WB], H1, R, H1, H2, nullptr, sv.d1, w.dt1, s))) return rc;
   // dense_att.linear: the history half over the rows, the candidate half over the users (d ct[b] = sum_s d t1[b, s])
-  if ((rc = launch_wgrad(w.dt1, H1, sv.all, R, U, H1, w.part, grads[P_WA], 2 * U, s))) return rc;
-  if ((rc = launch_colsum(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dt1, H1, sv.all, R, U, H1, w.part, grads[P_WA], 2 * U, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
   if ((rc = launch_dx(w.dt1, H1, params[P_WA], 2 * U, R, U, H1, w.dall, nullptr, w.dall, s))) return rc;
   hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((H1 + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.dt1, H1, 0,
                      (const float*)nullptr, 0, (const float*)nullptr, Si, H1, d1, false, w.dct);
   MANNER_LAUNCH_CHECK();
-  if ((rc = launch_wgrad(w.dct, H1, sv.cd, B, D, H1, w.part, grads[P_WA] + U, 2 * U, s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dct, H1, sv.cd, B, D, H1, w.part, grads[P_WA] + U, 2 * U, s))) return rc;
   // d cd[b] = dout[b] user[b] + d ct[b] Wa[:, U:] (the window and self-attention routes are added at the end)
   hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, w.wq, sv.all, U, 0, (const float*)nullptr, 0,
                      (const float*)nullptr, Si, U, d1, false, w.dcd);
   MANNER_LAUNCH_CHECK();
   if ((rc = launch_dx(w.dct, H1, params[P_WA] + U, 2 * U, B, D, H1, w.dcd, nullptr, w.dcd, s))) return rc;
   // linear3 and dropout3
-  if ((rc = launch_wgrad(w.dall, U, sv.cat, R, FU, U, w.part, grads[P_W3], FU, s))) return rc;
-  if ((rc = launch_colsum(w.dall, U, R, U, grads[P_B3], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dall, U, sv.cat, R, FU, U, w.part, grads[P_W3], FU, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dall, U, R, U, grads[P_B3], s))) return rc;
   if ((rc = launch_dx(w.dall, U, params[P_W3], FU, R, FU, U, nullptr, nullptr, w.dcat, s))) return rc;
   if (p > 0.f) {
     hipLaunchKernelGGL(drop_inplace_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, w.dcat, R * FU, d3);
     MANNER_LAUNCH_CHECK();
   }
   // candi-selfatt: out-projection, attention, in-projection, linear2
-  if ((rc = launch_wgrad(w.dcat + F, FU, sv.att, R, U, U, w.part, grads[P_WOUT], U, s))) return rc;
-  if ((rc = launch_colsum(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dcat + F, FU, sv.att, R, U, U, w.part, grads[P_WOUT], U, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
   if ((rc = launch_dx(w.dcat + F, FU, params[P_WOUT], U, R, U, U, nullptr, nullptr, w.datt, s))) return rc;
   if ((rc = launch_a0any_bwd_q(sv.qkv, sv.att, w.datt, w.dqkv, sv.stats, B, S, U, heads, s))) return rc;
   if ((rc = launch_a0any_bwd_kv(sv.qkv, w.datt, sv.stats, w.dqkv, B, S, U, heads, s))) return rc;
-  if ((rc = launch_wgrad(w.dqkv, 3 * U, sv.h2, R, U, 3 * U, w.part, grads[P_WIN], U, s))) return rc;
-  if ((rc = launch_colsum(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dqkv, 3 * U, sv.h2, R, U, 3 * U, w.part, grads[P_WIN], U, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
   // the K third of d in_proj_bias is zero in exact arithmetic (a shift of every key moves every logit of a row alike)
   MANNER_HIP_TRY(hipMemsetAsync(grads[P_BIN] + U, 0, (size_t)U * sizeof(float), s));
   if ((rc = launch_dx(w.dqkv, 3 * U, params[P_WIN], U, R, U, 3 * U, nullptr, nullptr, w.dh2, s))) return rc;
-  if ((rc = launch_wgrad(w.dh2, U, sv.a2, R, 2 * D, U, w.part, grads[P_W2], 2 * D, s))) return rc;
-  if ((rc = launch_colsum(w.dh2, U, R, U, grads[P_B2], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dh2, U, sv.a2, R, 2 * D, U, w.part, grads[P_W2], 2 * D, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dh2, U, R, U, grads[P_B2], s))) return rc;
   if ((rc = launch_dx(w.dh2, U, params[P_W2], 2 * D, R, 2 * D, U, nullptr, nullptr, w.da2, s))) return rc;
   // candi-cnn: linear1 from cat[:, :F]
-  if ((rc = launch_wgrad(w.dcat, FU, sv.a1, R, 4 * D, F, w.part, grads[P_W1], 4 * D, s))) return rc;
-  if ((rc = launch_colsum(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
+  if ((rc = launch_wgrad_rows(w.dcat, FU, sv.a1, R, 4 * D, F, w.part, grads[P_W1], 4 * D, s))) return rc;
+  if ((rc = launch_colsum_rows(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
   if ((rc = launch_dx(w.dcat, FU, params[P_W1], 4 * D, R, 4 * D, F, nullptr, nullptr, w.da1, s))) return rc;
   // d x: the three windows and the self-attention operand; d c: the sums over the slots, through dropout1
   hipLaunchKernelGGL(window_dx_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, w.da1, w.da2, Si, D, d2, grad_x);
@@ -1487,7 +1387,7 @@ int manner_hip_caum_scores_all(const float* x, const float* cand, const float* c
   const int64_t passes = (C + cp - 1) / cp;
   cp = (C + passes - 1) / passes;                          // as many passes, of even width (no last pass of one column)
   hipStream_t s = (hipStream_t)stream;
-  Bump bump(workspace);
+  FloatBump bump(workspace);
   AllBufs w;
   plan_all(bump, w, m, C, cp);
   const int64_t R = m.R, N = B * C;
@@ -1499,7 +1399,7 @@ int manner_hip_caum_scores_all(const float* x, const float* cand, const float* c
   if ((rc = launch_wlin(false, w.win, 3 * D, params[P_W1], 4 * D, params[P_B1], none, none, flat, R, 3 * D, F, w.wx, F, s))) return rc;
   if ((rc = launch_wlin(false, x, D, params[P_W2] + D, 2 * D, params[P_B2], none, none, flat, R, D, U, w.hx, U, s))) return rc;
   if ((rc = launch_wlin(false, w.hx, U, params[P_WIN], U, params[P_BIN], none, none, flat, R, U, 3 * U, w.qh, 3 * U, s))) return rc;
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)(((int64_t)U * U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, params[P_WOUT], U, w.owt);
+  hipLaunchKernelGGL(transpose_square_kernel, dim3((unsigned)(((int64_t)U * U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, params[P_WOUT], U, w.owt);
   MANNER_LAUNCH_CHECK();
   if ((rc = launch_wlin(false, params[P_W3] + F, FU, w.owt, U, none, none, none, flat, U, U, U, w.fold, U, s))) return rc;
   if ((rc = launch_wlin(false, params[P_BOUT], U, params[P_W3] + F, FU, params[P_B3], none, none, flat, 1, U, U, w.ba, U, s))) return rc;
@@ -1559,7 +1459,7 @@ int manner_hip_wgrad_rows_f32(const float* dy, int32_t ldy, const float* x, int3
 size_t manner_hip_caum_train_all_saved_bytes(int64_t B, int64_t S, int64_t C, int32_t D, int32_t F, int32_t U, int32_t H1, int32_t H2, int32_t heads) {
   if (B <= 0 || S <= 0 || C <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
   const Dims m{B * C, S, B * C * S, D, F, U, H1, H2, heads};
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Saved s;
   plan_saved(b, s, m);
   return b.off * sizeof(float) + 256;
@@ -1578,7 +1478,7 @@ int manner_hip_caum_train_all_forward(const float* x, const float* cand, const f
     if (!params[i]) return fail(MANNER_HIP_E_INVALID, "caum_train_all: null parameter %d", i);
   if (saved_bytes < manner_hip_caum_train_all_saved_bytes(B, S, C, D, F, U, H1, H2, heads)) return fail(MANNER_HIP_E_WORKSPACE, "caum_train_all: saved buffer too small");
   hipStream_t s = (hipStream_t)stream;
-  Bump bump(saved);
+  FloatBump bump(saved);
   Saved sv;
   plan_saved(bump, sv, m);
   const int64_t R = m.R, P = m.B;
@@ -1616,7 +1516,7 @@ size_t manner_hip_caum_train_all_backward_workspace_bytes(int64_t B, int64_t S, 
                                                           int32_t heads) {
   if (B <= 0 || S <= 0 || C <= 0 || D <= 0 || F <= 0 || U <= 0 || H1 <= 0 || H2 <= 0 || heads <= 0) return 0;
   const Dims m{B * C, S, B * C * S, D, F, U, H1, H2, heads};
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   WorkAll w;
   plan_work_all(b, w, m);
   return b.off * sizeof(float) + 256;
@@ -1651,7 +1551,7 @@ int manner_hip_caum_train_all_backward(const float* const* params, const float* 
     return fail(MANNER_HIP_E_WORKSPACE, "caum_train_all_backward: saved buffer too small");
   if (workspace_bytes < manner_hip_caum_train_all_backward_workspace_bytes(B, S, C, D, F, U, H1, H2, heads))
     return fail(MANNER_HIP_E_WORKSPACE, "caum_train_all_backward: workspace too small");
-  Bump bs(saved), bw(workspace);
+  FloatBump bs(saved), bw(workspace);
   Saved sv;
   WorkAll wa;
   plan_saved(bs, sv, m);
@@ -1673,11 +1573,11 @@ int manner_hip_caum_train_all_backward(const float* const* params, const float* 
   MANNER_HIP_TRY(hipMemsetAsync(grads[P_BC], 0, sizeof(float), s));
   // dense_att.linear2
   if ((rc = launch_wgrad_all(w.dt2, H2, sv.t1, R, H1, H2, part, grads[P_WB], H1, s))) return rc;
-  if ((rc = launch_colsum(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
+  if ((rc = launch_colsum_rows(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
   if ((rc = launch_mdx(w.dt2, H2, params[P_WB], H1, R, H1, H2, nullptr, sv.d1, w.dt1, wt, s))) return rc;
   // dense_att.linear: the history half over the rows, the candidate half over the (user, column) pairs (d ct[b, c] = sum_s d t1[b, c, s])
   if ((rc = launch_wgrad_all(w.dt1, H1, sv.all, R, U, H1, part, grads[P_WA], 2 * U, s))) return rc;
-  if ((rc = launch_colsum(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
+  if ((rc = launch_colsum_rows(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
   if ((rc = launch_mdx(w.dt1, H1, params[P_WA], 2 * U, R, U, H1, w.dall, nullptr, wa.dall2, wt, s))) return rc;
   hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)P, (unsigned)((H1 + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.dt1, H1, 0,
                      (const float*)nullptr, 0, (const float*)nullptr, Si, H1, d1, false, w.dct);
@@ -1690,7 +1590,7 @@ int manner_hip_caum_train_all_backward(const float* const* params, const float* 
   if ((rc = launch_mdx(w.dct, H1, params[P_WA] + U, 2 * U, P, D, H1, w.dcd, nullptr, wa.dcd2, wt, s))) return rc;
   // linear3 and dropout3
   if ((rc = launch_wgrad_all(wa.dall2, U, sv.cat, R, FU, U, part, grads[P_W3], FU, s))) return rc;
-  if ((rc = launch_colsum(wa.dall2, U, R, U, grads[P_B3], s))) return rc;
+  if ((rc = launch_colsum_rows(wa.dall2, U, R, U, grads[P_B3], s))) return rc;
   if ((rc = launch_mdx(wa.dall2, U, params[P_W3], FU, R, FU, U, nullptr, nullptr, w.dcat, wt, s))) return rc;
   if (p > 0.f) {
     hipLaunchKernelGGL(drop_cols_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, w.dcat, R * FU, Si, Ci, FU, d3, seeds);
@@ -1698,21 +1598,21 @@ int manner_hip_caum_train_all_backward(const float* const* params, const float* 
   }
   // candi-selfatt: out-projection, attention, in-projection, linear2
   if ((rc = launch_wgrad_all(w.dcat + F, FU, sv.att, R, U, U, part, grads[P_WOUT], U, s))) return rc;
-  if ((rc = launch_colsum(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
+  if ((rc = launch_colsum_rows(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
   if ((rc = launch_mdx(w.dcat + F, FU, params[P_WOUT], U, R, U, U, nullptr, nullptr, w.datt, wt, s))) return rc;
   if ((rc = launch_a0any_bwd_q(sv.qkv, sv.att, w.datt, w.dqkv, sv.stats, B, C * S, U, heads, s))) return rc;
   if ((rc = launch_a0any_bwd_kv(sv.qkv, w.datt, sv.stats, w.dqkv, B, C * S, U, heads, s))) return rc;
   if ((rc = launch_wgrad_all(w.dqkv, 3 * U, sv.h2, R, U, 3 * U, part, grads[P_WIN], U, s))) return rc;
-  if ((rc = launch_colsum(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
+  if ((rc = launch_colsum_rows(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
   // the K third of d in_proj_bias is zero in exact arithmetic (a shift of every key moves every logit of a row alike)
   MANNER_HIP_TRY(hipMemsetAsync(grads[P_BIN] + U, 0, (size_t)U * sizeof(float), s));
   if ((rc = launch_mdx(w.dqkv, 3 * U, params[P_WIN], U, R, U, 3 * U, nullptr, nullptr, w.dh2, wt, s))) return rc;
   if ((rc = launch_wgrad_all(w.dh2, U, sv.a2, R, 2 * D, U, part, grads[P_W2], 2 * D, s))) return rc;
-  if ((rc = launch_colsum(w.dh2, U, R, U, grads[P_B2], s))) return rc;
+  if ((rc = launch_colsum_rows(w.dh2, U, R, U, grads[P_B2], s))) return rc;
   if ((rc = launch_mdx(w.dh2, U, params[P_W2], 2 * D, R, 2 * D, U, nullptr, nullptr, w.da2, wt, s))) return rc;
   // candi-cnn: linear1 from cat[:, :F]
   if ((rc = launch_wgrad_all(w.dcat, FU, sv.a1, R, 4 * D, F, part, grads[P_W1], 4 * D, s))) return rc;
-  if ((rc = launch_colsum(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
+  if ((rc = launch_colsum_rows(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
   if ((rc = launch_mdx(w.dcat, FU, params[P_W1], 4 * D, R, 4 * D, F, nullptr, nullptr, w.da1, wt, s))) return rc;
   // d x: per column the three windows and the self-attention operand through the column's dropout2, the columns added in ascending c;
   // d cand: the sums over the slots, through the column's dropout1

@@ -225,4 +225,34 @@ int wlin_f32(bool tanh_act, const float* x, int ldx, const float* W, int ldw, co
 // dx [R, K] = dy [R, O] W [O, K] on the same kernel: W (rows ldw apart) is transposed into wt [K, O] first; R >= 1
 int wlin_dx_f32(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, float* dx, float* wt, hipStream_t stream);
 
+// ------------------------------------------------------------------ f32 row kernels of the side operators (rows_f32.hip)
+// gi [R, O] = b + x_r W^T over the rows r = (b S + t) C + c of x (row at x + b xsb + t xss + c K, zeros where t >= len[b]; C = 1: the
+// plain (b, t) rows); W [O, K]; xs (may be NULL) [R, K] receives the rows as read
+int launch_proj_rows(const float* x, int64_t xsb, int64_t xss, const int64_t* len, const float* W, const float* b, int S, int C, int64_t R, int K, int O,
+                     float* gi, float* xs, hipStream_t stream);
+// dW [O, K] (rows ldo apart) = sum_r dy[r, o] x[r, k]: dy rows ldy apart, x [R, K] contiguous, R >= 1.  The rows are summed in
+// wgrad_rows_groups(R) groups; part holds wgrad_rows_part_floats(R, K, O) floats (unused, may be NULL, with one group)
+constexpr int WGRAD_MAX_GROUPS = 16, WGRAD_GROUP_ROWS = 64;      // row groups at most, rows per group at least
+int wgrad_rows_groups(int64_t R);
+size_t wgrad_rows_part_floats(int64_t R, int K, int O);
+int launch_wgrad_rows(const float* dy, int ldy, const float* x, int64_t R, int K, int O, float* part, float* dW, int ldo, hipStream_t stream);
+// dW[o, k] = sum of part[g][o][k] over g < G in ascending g (the second half of launch_wgrad_rows, for another producer of part)
+int launch_wgrad_reduce(const float* part, int K, int O, int G, float* dW, int ldo, hipStream_t stream);
+// db [O] = sum_r dy[r, o], dy rows ldy apart
+int launch_colsum_rows(const float* dy, int ldy, int64_t R, int O, float* db, hipStream_t stream);
+// out [K, O] = in^T, in [O, K] rows ldw apart
+int launch_transpose_tile(const float* in, int ldw, int O, int K, float* out, hipStream_t stream);
+
+// Carves float buffers, each aligned to 64 floats, out of one allocation; a NULL base only measures (off = floats needed)
+struct FloatBump {
+  float* base;
+  size_t off = 0;
+  explicit FloatBump(void* p) : base(static_cast<float*>(p)) {}
+  float* take(size_t n) {
+    float* p = base ? base + off : nullptr;
+    off += (n + 63) / 64 * 64;
+    return p;
+  }
+};
+
 }  // namespace manner

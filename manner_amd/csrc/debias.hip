@@ -14,17 +14,17 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "row_head.h"
 
 namespace manner {
 namespace {
 
-constexpr int DB_MAX_D = 1024;                           // a row (news vector, or hidden activation) in registers: 16 floats per lane
-constexpr int DB_MAX_C = 64, DB_MAX_O = 64;              // classes of the table; outputs of the discriminator (one per lane)
-constexpr int DB_J = DB_MAX_D / 64;
-constexpr int DB_WG_ROWS = 8, DB_MAX_WG = 512;           // rows a workgroup takes per trip of its grid-stride loop; the grid's cap
-constexpr int DB_CHUNK_ROWS = 32, DB_MAX_CHUNKS = 128;   // binned sums: rows per partial sum at least; partial sums at most
-constexpr size_t DB_STAGE_BYTES = 128 * 1024;            // a W2 up to here is staged in LDS, a larger one is read through L2
+// the row kernels here walk as row_head.h's do and bin as its weight gradient does
+constexpr int DB_MAX_D = RH_MAX_D;                       // a row (news vector, or hidden activation) in registers: 16 floats per lane
+constexpr int DB_MAX_C = 64, DB_MAX_O = RH_MAX_O;        // classes of the table; outputs of the discriminator (one per lane)
+constexpr int DB_J = RH_J;
+constexpr int DB_WG_ROWS = RH_WG_ROWS;                   // rows a workgroup takes per trip of its grid-stride loop
+constexpr int DB_CHUNK_ROWS = RH_CHUNK_ROWS, DB_MAX_CHUNKS = RH_MAX_CHUNKS;      // binned sums: rows per partial sum at least; partial sums at most
 constexpr float DB_EPS = 1e-8f;
 
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }      // torch's sign: 0 at 0 and at NaN
@@ -270,131 +270,24 @@ __global__ __launch_bounds__(256) void db_score_grad_kernel(const float* __restr
   out[e] = a;
 }
 
-// ---------------------------------------------------------------- the adversarial head, layer 2
-// Over the hidden rows h [N, H]: logits = W2 h + b2 (class o's logit kept in lane o), the softmax across the lanes, the row's
-// cross-entropy against class (cls - 1) mod O — the module writes y_true[i, t - 1] = 1, so class 0 lands on the last column —
-// -> rowloss [N]; `saved` [N, O] (may be NULL) = (p - y) / (rows of the row's segment).  STAGED: W2 in LDS.
-template <bool STAGED>
-__global__ __launch_bounds__(256) void db_head_fwd_kernel(const float* __restrict__ h, const float* __restrict__ W, const float* __restrict__ bias,
-                                                          const int64_t* __restrict__ cls, int64_t n0, int64_t N, int H, int O,
-                                                          float* __restrict__ rowloss, float* __restrict__ saved, int32_t* __restrict__ status) {
-  extern __shared__ __attribute__((aligned(16))) float wl[];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (STAGED) stage_weight(W, O * H, wl);
-  const float* w = STAGED ? wl : W;
-  const float bl = lane < O ? bias[lane] : 0.f;
-  for (int64_t base = (int64_t)blockIdx.x * DB_WG_ROWS; base < N; base += (int64_t)gridDim.x * DB_WG_ROWS) {
-    const int64_t end = base + DB_WG_ROWS < N ? base + DB_WG_ROWS : N;
-    for (int64_t r = base + wave; r < end; r += 4) {
-      float xr[DB_J];
-      load_row(h + (size_t)r * H, H, lane, xr);
-      float mine = -INFINITY;                                   // the logit of class `lane`
-      for (int o0 = 0; o0 < O; o0 += 4) {
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < DB_J; ++j) {
-          if (64 * j < H) {                                      // wave-uniform; a lane past H holds 0 and reads column H - 1
-            const int d = min(lane + 64 * j, H - 1);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) a[c] = fmaf(xr[j], w[min(o0 + c, O - 1) * H + d], a[c]);
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float t = wsum(a[c]);
-          if (lane == o0 + c && o0 + c < O) mine = t + bl;
-        }
-      }
-      const int64_t t = cls[r];
-      const bool bad = t < 0 || t >= O;
-      const int tt = bad ? 0 : (t == 0 ? O - 1 : (int)t - 1);
-      const float m = wmax(mine);
-      const float e = lane < O ? expf(mine - m) : 0.f;
-      const float s = wsum(e);
-      const float lt = __shfl(mine, tt, 64);
-      const float inv = 1.0f / (float)(r < n0 ? n0 : N - n0);
-      if (lane < O && saved) saved[(size_t)r * O + lane] = bad ? 0.f : (e / s - (lane == tt ? 1.f : 0.f)) * inv;
-      if (lane == 0) {
-        rowloss[r] = bad ? 0.f : (logf(s) + m) - lt;
-        if (bad && status) atomicOr(status, MANNER_HIP_STATUS_INDEX);
-      }
-    }
-  }
-}
-
+// ---------------------------------------------------------------- the adversarial head, layer 2 (row_head.h)
+// Over the hidden rows h [N, H]: the row's cross-entropy against class (cls - 1) mod O — the module writes y_true[i, t - 1] = 1, so class 0
+// lands on the last column; `saved` [N, O] = (p - y) / (rows of the row's segment: n0 history rows, then N - n0 candidate rows).
+struct DbHead {
+  int64_t n0;
+  __device__ __forceinline__ int column(int64_t t, int O) const { return t == 0 ? O - 1 : (int)t - 1; }
+  __device__ __forceinline__ float scaled(float v, int64_t r, int64_t N) const { return v * (1.0f / (float)(r < n0 ? n0 : N - n0)); }
+  __device__ __forceinline__ void keep_logit(float, size_t) const {}
+};
 // dpre[r, k] = (g sum_o saved[r, o] W2[o, k], ascending o) (1 - h[r, k]^2): the gradient at layer 1's pre-activation
-template <bool STAGED>
-__global__ __launch_bounds__(256) void db_head_dpre_kernel(const float* __restrict__ g, const float* __restrict__ W, const float* __restrict__ saved,
-                                                           const float* __restrict__ h, int64_t N, int H, int O, float* __restrict__ dpre) {
-  extern __shared__ __attribute__((aligned(16))) float wl[];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (STAGED) stage_weight(W, O * H, wl);
-  const float* w = STAGED ? wl : W;
-  const float g0 = g[0];
-  for (int64_t base = (int64_t)blockIdx.x * DB_WG_ROWS; base < N; base += (int64_t)gridDim.x * DB_WG_ROWS) {
-    const int64_t end = base + DB_WG_ROWS < N ? base + DB_WG_ROWS : N;
-    for (int64_t r = base + wave; r < end; r += 4) {
-      const float mine = lane < O ? saved[(size_t)r * O + lane] : 0.f;
-      float a[DB_J];
-#pragma unroll
-      for (int j = 0; j < DB_J; ++j) a[j] = 0.f;
-      for (int o = 0; o < O; ++o) {
-        const float t = __shfl(mine, o, 64);
-#pragma unroll
-        for (int j = 0; j < DB_J; ++j)
-          if (64 * j < H) a[j] = fmaf(t, w[o * H + min(lane + 64 * j, H - 1)], a[j]);      // wave-uniform guard, clamped column
-      }
-#pragma unroll
-      for (int j = 0; j < DB_J; ++j) {
-        const int k = lane + 64 * j;
-        if (k < H) {
-          const float hv = h[(size_t)r * H + k];
-          dpre[(size_t)r * H + k] = (g0 * a[j]) * (1.0f - hv * hv);
-        }
-      }
-    }
+struct DbDpre {
+  const float* h;
+  __device__ __forceinline__ float coef(float g, int64_t) const { return g; }
+  __device__ __forceinline__ float operator()(float v, size_t at) const {
+    const float hv = h[at];
+    return v * (1.0f - hv * hv);
   }
-}
-
-// part[chunk][o][kk] = the sum over the chunk's rows, ascending, of saved[r, o] (kk < H ? h[r, kk] : 1): d W2 and, as column H, d b2.
-// One wave per (64 columns, chunk): lane = column, the O classes in registers.
-template <int OC>
-__global__ __launch_bounds__(64) void db_head_wgrad_kernel(const float* __restrict__ h, const float* __restrict__ saved, int64_t N, int H, int O,
-                                                           int64_t chunk_rows, float* __restrict__ part) {
-  const int lane = threadIdx.x;
-  const int kk = blockIdx.x * 64 + lane;
-  const int64_t r0 = (int64_t)blockIdx.y * chunk_rows, r1 = r0 + chunk_rows < N ? r0 + chunk_rows : N;
-  float acc[OC];
-#pragma unroll
-  for (int c = 0; c < OC; ++c) acc[c] = 0.f;
-  for (int64_t r = r0; r < r1; ++r) {
-    const float xv = kk < H ? h[(size_t)r * H + kk] : (kk == H ? 1.f : 0.f);
-    const float mine = lane < O ? saved[(size_t)r * O + lane] : 0.f;
-#pragma unroll
-    for (int c = 0; c < OC; ++c)
-      if (c < O) acc[c] = fmaf(__shfl(mine, c, 64), xv, acc[c]);
-  }
-  if (kk <= H) {
-#pragma unroll
-    for (int c = 0; c < OC; ++c)
-      if (c < O) part[((size_t)blockIdx.y * O + c) * (H + 1) + kk] = acc[c];
-  }
-}
-// one thread per (o, column): the chunks in ascending order, times g
-__global__ __launch_bounds__(256) void db_head_wreduce_kernel(const float* __restrict__ g, const float* __restrict__ part, int H, int O, int chunks,
-                                                              float* __restrict__ dW, float* __restrict__ db) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= O * (H + 1)) return;
-  const int o = i / (H + 1), kk = i - o * (H + 1);
-  float a = 0.f;
-  for (int c = 0; c < chunks; ++c) a += part[(size_t)c * O * (H + 1) + i];
-  a *= g[0];
-  if (kk < H) {
-    if (dW) dW[(size_t)o * H + kk] = a;
-  } else if (db) {
-    db[o] = a;
-  }
-}
+};
 // d b1: part[chunk][k] = the sum of dpre[r, k] over the chunk's rows, ascending; then the chunks in ascending order
 __global__ __launch_bounds__(64) void db_colsum_kernel(const float* __restrict__ v, int64_t N, int H, int64_t chunk_rows, float* __restrict__ part) {
   const int k = blockIdx.x * 64 + threadIdx.x;
@@ -413,16 +306,12 @@ __global__ __launch_bounds__(256) void db_colsum_reduce_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------- host side
-unsigned walk_grid(int64_t N) {
-  const int64_t g = (N + DB_WG_ROWS - 1) / DB_WG_ROWS;
-  return (unsigned)(g < DB_MAX_WG ? g : DB_MAX_WG);
-}
 int64_t bin_chunks(int64_t M) {
   const int64_t c = (M + DB_CHUNK_ROWS - 1) / DB_CHUNK_ROWS;
   return std::max<int64_t>(1, c < DB_MAX_CHUNKS ? c : DB_MAX_CHUNKS);
 }
 size_t aligned(size_t bytes) { return (bytes + 255) / 256 * 256; }
-bool staged(int H, int O) { return (size_t)O * H * sizeof(float) <= DB_STAGE_BYTES; }
+bool staged(int H, int O) { return (size_t)O * H * sizeof(float) <= RH_STAGE_BYTES; }
 
 int table_check(const char* who, int64_t N, int D, int C) {
   if (N < 0 || D < 1 || C < 1) return fail(MANNER_HIP_E_INVALID, "%s: bad shape N=%lld D=%d C=%d", who, (long long)N, D, C);
@@ -485,11 +374,6 @@ AdvBwd adv_bwd_plan(int64_t N, int D, int H, int O) {
   return p;
 }
 
-template <int OC>
-void launch_head_wgrad(const float* h, const float* saved, int64_t N, int H, int O, int64_t chunks, int64_t chunk_rows, float* part, hipStream_t s) {
-  hipLaunchKernelGGL(db_head_wgrad_kernel<OC>, dim3((unsigned)((H + 1 + 63) / 64), (unsigned)chunks), dim3(64), 0, s, h, saved, N, H, O, chunk_rows, part);
-}
-
 }  // namespace
 }  // namespace manner
 
@@ -516,11 +400,11 @@ int manner_hip_orth_loss(const float* rows, int64_t N, int64_t n_hist, const flo
   float* cosv = static_cast<float*>(workspace);
   float* ucos = cosv + N;
   if (N > 0) {
-    hipLaunchKernelGGL(db_cos_fwd_kernel, dim3(walk_grid(N)), dim3(256), 0, s, rows, table, cls, N, D, C, cosv, status);
+    hipLaunchKernelGGL(db_cos_fwd_kernel, dim3(rh_walk_grid(N)), dim3(256), 0, s, rows, table, cls, N, D, C, cosv, status);
     MANNER_LAUNCH_CHECK();
   }
   if (B > 0) {
-    hipLaunchKernelGGL(db_cos_fwd_kernel, dim3(walk_grid(B)), dim3(256), 0, s, user_free, user_aware, (const int64_t*)nullptr, B, D, C, ucos,
+    hipLaunchKernelGGL(db_cos_fwd_kernel, dim3(rh_walk_grid(B)), dim3(256), 0, s, user_free, user_aware, (const int64_t*)nullptr, B, D, C, ucos,
                        (int32_t*)nullptr);
     MANNER_LAUNCH_CHECK();
   }
@@ -549,13 +433,13 @@ int manner_hip_orth_loss_backward(const float* grad_loss, const float* means, co
     part = reinterpret_cast<float*>(static_cast<char*>(workspace) + aligned((size_t)2 * N * sizeof(float)));
   }
   if (N > 0 && (grad_rows || grad_table)) {
-    hipLaunchKernelGGL(db_cos_bwd_kernel, dim3(walk_grid(N)), dim3(256), 0, s, grad_loss, means, rows, table, cls, n_hist, N, D, C, grad_rows,
+    hipLaunchKernelGGL(db_cos_bwd_kernel, dim3(rh_walk_grid(N)), dim3(256), 0, s, grad_loss, means, rows, table, cls, n_hist, N, D, C, grad_rows,
                        (float*)nullptr, pq);
     MANNER_LAUNCH_CHECK();
   }
   if (grad_table && (rc = launch_bins(false, rows, pq, cls, nullptr, 1, N, N, D, C, table, part, grad_table, s))) return rc;
   if (B > 0 && (grad_user_free || grad_user_aware)) {
-    hipLaunchKernelGGL(db_cos_bwd_kernel, dim3(walk_grid(B)), dim3(256), 0, s, grad_loss, means, user_free, user_aware, (const int64_t*)nullptr,
+    hipLaunchKernelGGL(db_cos_bwd_kernel, dim3(rh_walk_grid(B)), dim3(256), 0, s, grad_loss, means, user_free, user_aware, (const int64_t*)nullptr,
                        (int64_t)0, B, D, C, grad_user_free, grad_user_aware, (float*)nullptr);
     MANNER_LAUNCH_CHECK();
   }
@@ -574,7 +458,7 @@ int manner_hip_class_dense(const float* table, const int64_t* cls, const int64_t
   if (M == 0) return MANNER_HIP_OK;
   if (!table || !off || !out || (N > 0 && !cls)) return fail(MANNER_HIP_E_INVALID, "class_dense: null pointer");
   const int64_t g = (M + 3) / 4;
-  hipLaunchKernelGGL(db_class_dense_kernel, dim3((unsigned)std::min<int64_t>(g, DB_MAX_WG)), dim3(256), 0, (hipStream_t)stream, table, cls, off, width, M, N, D,
+  hipLaunchKernelGGL(db_class_dense_kernel, dim3((unsigned)std::min<int64_t>(g, RH_MAX_WG)), dim3(256), 0, (hipStream_t)stream, table, cls, off, width, M, N, D,
                      C, out, status);
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
@@ -655,16 +539,10 @@ int manner_hip_adv_loss(const float* rows, int64_t N, int64_t n_hist, const floa
   float* rowloss = static_cast<float*>(workspace);
   if (N > 0) {
     if ((rc = wlin_f32(true, rows, D, w1, D, b1, N, D, H, hidden, H, s))) return rc;
-    const dim3 grid(walk_grid(N)), block(256);
-    if (staged(H, O)) {
-      const size_t lds = (size_t)O * H * sizeof(float);
-      if (lds > 64 * 1024)
-        MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(db_head_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DB_STAGE_BYTES));
-      hipLaunchKernelGGL(db_head_fwd_kernel<true>, grid, block, lds, s, hidden, w2, b2, cls, n_hist, N, H, O, rowloss, saved, status);
-    } else {
-      hipLaunchKernelGGL(db_head_fwd_kernel<false>, grid, block, 0, s, hidden, w2, b2, cls, n_hist, N, H, O, rowloss, saved, status);
-    }
-    MANNER_LAUNCH_CHECK();
+    const DbHead head{n_hist};
+    if (staged(H, O)) rc = rh_launch_walk(rh_head_fwd_kernel<0, DbHead>, true, N, H, O, s, hidden, w2, b2, cls, head, N, H, O, rowloss, saved, status);
+    else rc = rh_launch_walk(rh_head_fwd_kernel<1, DbHead>, false, N, H, O, s, hidden, w2, b2, cls, head, N, H, O, rowloss, saved, status);
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(db_segment_means_kernel<false>, dim3(1), dim3(256), 0, s, rowloss, n_hist, N, (const float*)nullptr, (int64_t)0, loss, (float*)nullptr);
   MANNER_LAUNCH_CHECK();
@@ -691,16 +569,10 @@ int manner_hip_adv_loss_backward(const float* grad_loss, const float* rows, int6
   float* dpre = reinterpret_cast<float*>(base + p.dpre);
   const int64_t chunks = bin_chunks(N), chunk_rows = (N + chunks - 1) / chunks;
   if (grad_rows || grad_w1 || grad_b1) {
-    const dim3 grid(walk_grid(N)), block(256);
-    if (staged(H, O)) {
-      const size_t lds = (size_t)O * H * sizeof(float);
-      if (lds > 64 * 1024)
-        MANNER_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(db_head_dpre_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DB_STAGE_BYTES));
-      hipLaunchKernelGGL(db_head_dpre_kernel<true>, grid, block, lds, s, grad_loss, w2, saved, hidden, N, H, O, dpre);
-    } else {
-      hipLaunchKernelGGL(db_head_dpre_kernel<false>, grid, block, 0, s, grad_loss, w2, saved, hidden, N, H, O, dpre);
-    }
-    MANNER_LAUNCH_CHECK();
+    const DbDpre last{hidden};
+    if (staged(H, O)) rc = rh_launch_walk(rh_head_dx_kernel<true, DbDpre>, true, N, H, O, s, grad_loss, w2, saved, last, N, H, O, dpre);
+    else rc = rh_launch_walk(rh_head_dx_kernel<false, DbDpre>, false, N, H, O, s, grad_loss, w2, saved, last, N, H, O, dpre);
+    if (rc) return rc;
   }
   if (grad_rows && (rc = wlin_dx_f32(dpre, H, w1, D, N, D, H, grad_rows, reinterpret_cast<float*>(base + p.wt), s))) return rc;
   if (grad_w1 && (rc = manner_hip_wgrad_rows_f32(dpre, H, rows, D, N, D, H, grad_w1, D, base + p.w1part, p.w2part - p.w1part, stream))) return rc;
@@ -712,14 +584,7 @@ int manner_hip_adv_loss_backward(const float* grad_loss, const float* rows, int6
     MANNER_LAUNCH_CHECK();
   }
   if (grad_w2 || grad_b2) {
-    float* part = reinterpret_cast<float*>(base + p.w2part);
-    if (O <= 8) launch_head_wgrad<8>(hidden, saved, N, H, O, chunks, chunk_rows, part, s);
-    else if (O <= 32) launch_head_wgrad<32>(hidden, saved, N, H, O, chunks, chunk_rows, part, s);
-    else launch_head_wgrad<64>(hidden, saved, N, H, O, chunks, chunk_rows, part, s);
-    MANNER_LAUNCH_CHECK();
-    hipLaunchKernelGGL(db_head_wreduce_kernel, dim3((unsigned)((O * (H + 1) + 255) / 256)), dim3(256), 0, s, grad_loss, part, H, O, (int)chunks, grad_w2,
-                       grad_b2);
-    MANNER_LAUNCH_CHECK();
+    if ((rc = rh_head_wgrad(grad_loss, 1.0f, hidden, saved, N, H, O, reinterpret_cast<float*>(base + p.w2part), grad_w2, grad_b2, s))) return rc;
   }
   return MANNER_HIP_OK;
 }

@@ -23,74 +23,10 @@ namespace {
 
 constexpr int GR_MAX_S = 256, GR_MAX_W = 1024;
 constexpr int GR_BLOCK = 256, GR_WAVE = 64, GR_WAVES = GR_BLOCK / GR_WAVE;
-constexpr int GR_ROWS = 8;           // batch rows per workgroup of the step kernels, rows per workgroup of the input projection
+constexpr int GR_ROWS = 8;           // batch rows per workgroup of the step kernels
 constexpr int GR_UNITS = GR_WAVES;   // hidden units per workgroup of the step kernels: one per wave
-constexpr int GR_OT = 64;            // output features per workgroup of the input projection
-constexpr int GR_KS = 128;           // input features per step of the input projection
-constexpr int GR_TT = 32;            // tile edge of the transpose
-constexpr int GR_ALIGN = 64;         // floats every saved / workspace buffer is aligned to
-static_assert(GR_OT * GR_WAVES == GR_BLOCK && GR_WAVES == 4 && GR_KS % GR_WAVES == 0, "proj_kernel: thread = (output feature, K quarter)");
 static_assert(GR_ROWS <= GR_WAVE, "lane rr of a wave finishes batch row rr");
 static_assert(GR_WAVE == 64, "common.h's wsum reduces 64 lanes");
-
-// ---------------------------------------------------------------- input projection
-// gi[r, o] = b[o] + sum_k x[b, t, k] W[o, k], r = b S + t; x[b, t, :] at x + b xsb + t xss, read as zeros where t >= len[b].
-// grid (ceil(R / GR_ROWS), ceil(O / GR_OT)); caum.hip's lin_kernel with the row addressing above: thread = (output feature, wave),
-// each wave a quarter of every K step on its own chain, the four partial sums added pairwise.  `xs` [R, K] (training): the rows as
-// they were read (zeros at the padded slots), for the weight gradient; written by the workgroups of the first output tile.
-__global__ __launch_bounds__(GR_BLOCK) void proj_kernel(const float* __restrict__ x, int64_t xsb, int64_t xss, const int64_t* __restrict__ len,
-                                                   const float* __restrict__ W, const float* __restrict__ b, int S, int64_t R, int K, int O,
-                                                   float* __restrict__ gi, float* __restrict__ xs) {
-  __shared__ float xt[GR_ROWS][GR_KS];
-  __shared__ float ws[GR_OT][GR_KS + 1];
-  __shared__ float red[GR_WAVES][GR_ROWS][GR_OT];
-  __shared__ const float* rowp[GR_ROWS];
-  const int64_t r0 = (int64_t)blockIdx.x * GR_ROWS;
-  const int nr = (int)min((int64_t)GR_ROWS, R - r0);
-  if (threadIdx.x < GR_ROWS) {
-    const float* p = nullptr;
-    if ((int)threadIdx.x < nr) {
-      const int64_t r = r0 + threadIdx.x, bb = r / S, t = r - bb * S;
-      if (t < len[bb]) p = x + bb * xsb + t * xss;
-    }
-    rowp[threadIdx.x] = p;
-  }
-  const int o0 = blockIdx.y * GR_OT, oc = threadIdx.x % GR_OT, kq = threadIdx.x / GR_OT;
-  float acc[GR_ROWS];
-#pragma unroll
-  for (int rr = 0; rr < GR_ROWS; ++rr) acc[rr] = 0.f;
-  for (int k0 = 0; k0 < K; k0 += GR_KS) {
-    const int kc = min(GR_KS, K - k0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < GR_ROWS * GR_KS; i += GR_BLOCK) {
-      const int rr = i / GR_KS, k = i - rr * GR_KS;
-      const float v = (rowp[rr] && k < kc) ? rowp[rr][k0 + k] : 0.f;
-      xt[rr][k] = v;
-      if (xs && blockIdx.y == 0 && rr < nr && k < kc) xs[(size_t)(r0 + rr) * K + k0 + k] = v;
-    }
-    for (int i = threadIdx.x; i < GR_OT * GR_KS; i += GR_BLOCK) {
-      const int oo = i / GR_KS, k = i - oo * GR_KS;
-      ws[oo][k] = (o0 + oo < O && k < kc) ? W[(size_t)(o0 + oo) * K + k0 + k] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = kq * (GR_KS / GR_WAVES); k < (kq + 1) * (GR_KS / GR_WAVES); ++k) {
-      const float wv = ws[oc][k];
-#pragma unroll
-      for (int rr = 0; rr < GR_ROWS; ++rr) acc[rr] = fmaf(xt[rr][k], wv, acc[rr]);
-    }
-  }
-#pragma unroll
-  for (int rr = 0; rr < GR_ROWS; ++rr) red[kq][rr][oc] = acc[rr];
-  __syncthreads();
-  const int o = o0 + oc;
-  if (kq == 0 && o < O) {
-    const float bv = b[o];
-#pragma unroll
-    for (int rr = 0; rr < GR_ROWS; ++rr)
-      if (rr < nr) gi[(size_t)(r0 + rr) * O + o] = ((red[0][rr][oc] + red[1][rr][oc]) + (red[2][rr][oc] + red[3][rr][oc])) + bv;
-  }
-}
 
 // ---------------------------------------------------------------- one time step
 // grid (ceil(H / GR_UNITS), ceil(B / GR_ROWS)).  hin [B, H] rows ldin apart (NULL: zeros), hout rows ldout apart (another buffer).
@@ -151,18 +87,6 @@ __global__ __launch_bounds__(GR_BLOCK) void step_kernel(const float* __restrict_
       hout[b * ldout + j] = hv;
     }
   }
-}
-
-// wt[k, o] = w[o, k]; w [O, K].  grid (ceil(K / GR_TT), ceil(O / GR_TT)), block GR_BLOCK = GR_TT x 8
-__global__ __launch_bounds__(GR_BLOCK) void transpose_kernel(const float* __restrict__ w, int O, int K, float* __restrict__ wt) {
-  __shared__ float tile[GR_TT][GR_TT + 1];
-  const int tx = threadIdx.x % GR_TT, ty = threadIdx.x / GR_TT;
-  const int k0 = blockIdx.x * GR_TT, o0 = blockIdx.y * GR_TT;
-  for (int i = ty; i < GR_TT; i += GR_BLOCK / GR_TT)
-    if (o0 + i < O && k0 + tx < K) tile[i][tx] = w[(size_t)(o0 + i) * K + k0 + tx];
-  __syncthreads();
-  for (int i = ty; i < GR_TT; i += GR_BLOCK / GR_TT)
-    if (k0 + i < K && o0 + tx < O) wt[(size_t)(k0 + i) * O + o0 + tx] = tile[tx][i];
 }
 
 // ---------------------------------------------------------------- one time step, backward
@@ -243,25 +167,15 @@ __global__ __launch_bounds__(GR_BLOCK) void user_rows_kernel(const int64_t* __re
   for (int c = threadIdx.x; c < E; c += GR_BLOCK) out[b * ldo + c] = m == 0.f ? 0.f : src[row * lds + c] * m;
 }
 
-struct Bump {
-  float* base;
-  size_t off = 0;
-  explicit Bump(void* p) : base(static_cast<float*>(p)) {}
-  float* take(size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + GR_ALIGN - 1) / GR_ALIGN * GR_ALIGN;
-    return p;
-  }
-};
 struct Saved { float *xs, *hs, *gates; };            // x rows [B S, I]; h_{t-1} [S, B, H]; r, z, n, W_hn h + b_hn [S, B, 4, H]
-void plan_saved(Bump& b, Saved& s, size_t B, size_t S, size_t I, size_t H) {
+void plan_saved(FloatBump& b, Saved& s, size_t B, size_t S, size_t I, size_t H) {
   s.xs = b.take(B * S * I);
   s.hs = b.take(S * B * H);
   s.gates = b.take(S * B * 4 * H);
 }
 // forward: gi, two h buffers; backward: W_hh^T, dgi [B S, 3H], dgh [S, B, 3H], two dh buffers — one size serves both
 struct Work { float *gi, *h[2], *wt, *dgh; };
-void plan_work(Bump& b, Work& w, size_t B, size_t S, size_t H) {
+void plan_work(FloatBump& b, Work& w, size_t B, size_t S, size_t H) {
   w.gi = b.take(B * S * 3 * H);
   w.h[0] = b.take(B * H);
   w.h[1] = b.take(B * H);
@@ -287,7 +201,7 @@ extern "C" {
 
 size_t manner_hip_gru_saved_bytes(int64_t B, int64_t S, int32_t I, int32_t H) {
   if (B <= 0 || S <= 0 || I <= 0 || H <= 0) return 0;
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Saved s;
   plan_saved(b, s, (size_t)B, (size_t)S, (size_t)I, (size_t)H);
   return b.off * sizeof(float) + 256;
@@ -295,7 +209,7 @@ size_t manner_hip_gru_saved_bytes(int64_t B, int64_t S, int32_t I, int32_t H) {
 
 size_t manner_hip_gru_workspace_bytes(int64_t B, int64_t S, int32_t I, int32_t H) {
   if (B <= 0 || S <= 0 || I <= 0 || H <= 0) return 0;
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Work w;
   plan_work(b, w, (size_t)B, (size_t)S, (size_t)H);
   return b.off * sizeof(float) + 256;
@@ -313,16 +227,14 @@ int manner_hip_gru_forward(const float* x, int64_t x_stride_b, int64_t x_stride_
   if (workspace_bytes < manner_hip_gru_workspace_bytes(B, S, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "gru: workspace too small");
   if (saved && saved_bytes < manner_hip_gru_saved_bytes(B, S, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "gru: saved buffer too small");
   hipStream_t s = (hipStream_t)stream;
-  Bump bw(workspace), bs(saved);
+  FloatBump bw(workspace), bs(saved);
   Work w;
   Saved sv;
   plan_work(bw, w, (size_t)B, (size_t)S, (size_t)H);
   plan_saved(bs, sv, (size_t)B, (size_t)S, (size_t)I, (size_t)H);
   const int64_t R = B * S;
   const int Si = (int)S;
-  hipLaunchKernelGGL(proj_kernel, dim3((unsigned)((R + GR_ROWS - 1) / GR_ROWS), (unsigned)((3 * H + GR_OT - 1) / GR_OT)), dim3(GR_BLOCK), 0, s, x,
-                     x_stride_b, x_stride_s, lengths, w_ih, b_ih, Si, R, I, 3 * H, w.gi, saved ? sv.xs : (float*)nullptr);
-  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_proj_rows(x, x_stride_b, x_stride_s, lengths, w_ih, b_ih, Si, 1, R, I, 3 * H, w.gi, saved ? sv.xs : nullptr, s))) return rc;
   const size_t BH = (size_t)B * H;
   if (saved) {                                       // hs[0] = h_0: the weight gradient reads it
     if (h0) MANNER_HIP_TRY(hipMemcpyAsync(sv.hs, h0, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -365,7 +277,7 @@ int manner_hip_gru_backward(const float* w_ih, const float* w_hh, const int64_t*
   if (ldg < H) return fail(MANNER_HIP_E_INVALID, "gru_backward: bad stride");
   if (saved_bytes < manner_hip_gru_saved_bytes(B, S, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "gru_backward: saved buffer too small");
   if (workspace_bytes < manner_hip_gru_workspace_bytes(B, S, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "gru_backward: workspace too small");
-  Bump bw(workspace), bs(saved);
+  FloatBump bw(workspace), bs(saved);
   Work w;
   Saved sv;
   plan_work(bw, w, (size_t)B, (size_t)S, (size_t)H);
@@ -373,9 +285,7 @@ int manner_hip_gru_backward(const float* w_ih, const float* w_hh, const int64_t*
   const int Si = (int)S;
   const size_t BH = (size_t)B * H;
   float* dgi = w.gi;                                 // the forward's gi is dead: its place holds d gi [B S, 3H]
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((H + GR_TT - 1) / GR_TT), (unsigned)((3 * H + GR_TT - 1) / GR_TT)), dim3(GR_BLOCK), 0, s, w_hh, 3 * H,
-                     (int)H, w.wt);
-  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_transpose_tile(w_hh, H, 3 * H, H, w.wt, s))) return rc;
   const dim3 grid((unsigned)((H + GR_UNITS - 1) / GR_UNITS), (unsigned)((B + GR_ROWS - 1) / GR_ROWS));
   const float* cur = grad_out;
   int64_t ldin = ldg;

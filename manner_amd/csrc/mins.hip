@@ -2,7 +2,7 @@
 //
 // Channel GRU: a one-layer GRU over R = B C independent sequences (row r = b C + c reads the channel c of user b: the columns
 // [c I, (c + 1) I) of x[b, t, :]) that all share one set of weights, every row returning its state after its own len[b] steps.
-//   gi = x W_ih^T + b_ih for all (b, t, c) rows in one launch (gru.hip's projection with the channel in the row address), then the
+//   gi = x W_ih^T + b_ih for all (b, t, c) rows in one launch (rows_f32.hip's projection, the channel in the row address), then the
 //   WHOLE RECURRENCE IN ONE LAUNCH: at H <= 128 the W_hh row of a (gate, unit) fits the registers of one thread, so a workgroup of
 //   3 x 128 threads — thread = (gate g, unit j), row j of W_g in 128 registers, zero past H — owns a tile of CG_ROWS rows for all S
 //   steps.  Per step: gh = h W_hh^T + b_hh into LDS (the tile's h rows are read from LDS as broadcasts), a workgroup barrier, the gates
@@ -31,68 +31,7 @@ constexpr int CG_MAX_S = 256, CG_MAX_I = 1024;
 constexpr int CG_HP = 128;               // register width of the recurrence: H <= CG_HP
 constexpr int CG_BLOCK = 3 * CG_HP;      // thread = (gate, unit)
 constexpr int CG_ROWS = 8;               // sequences per workgroup of the recurrence kernels
-constexpr int CG_ALIGN = 64;             // floats every saved / workspace buffer is aligned to
-constexpr int PJ_BLOCK = 256, PJ_WAVES = 4, PJ_ROWS = 8, PJ_OT = 64, PJ_KS = 128;      // the input projection: gru.hip's tiling
-static_assert(PJ_OT * PJ_WAVES == PJ_BLOCK && PJ_KS % PJ_WAVES == 0, "cproj_kernel: thread = (output feature, K quarter)");
 static_assert(CG_HP % 4 == 0, "the h rows are read as float4");
-
-
-// ---------------------------------------------------------------- input projection
-// gi[r, o] = b[o] + sum_k x[b, t, c I + k] W[o, k], r = (b S + t) C + c; the row is read as zeros where t >= len[b].  `xs` [R, K]
-// (training): the rows as they were read.  grid (ceil(R / PJ_ROWS), ceil(O / PJ_OT))
-__global__ __launch_bounds__(PJ_BLOCK) void cproj_kernel(const float* __restrict__ x, int64_t xsb, int64_t xss, const int64_t* __restrict__ len,
-                                                    const float* __restrict__ W, const float* __restrict__ b, int S, int C, int64_t R, int K, int O,
-                                                    float* __restrict__ gi, float* __restrict__ xs) {
-  __shared__ float xt[PJ_ROWS][PJ_KS];
-  __shared__ float ws[PJ_OT][PJ_KS + 1];
-  __shared__ float red[PJ_WAVES][PJ_ROWS][PJ_OT];
-  __shared__ const float* rowp[PJ_ROWS];
-  const int64_t r0 = (int64_t)blockIdx.x * PJ_ROWS;
-  const int nr = (int)min((int64_t)PJ_ROWS, R - r0);
-  if (threadIdx.x < PJ_ROWS) {
-    const float* p = nullptr;
-    if ((int)threadIdx.x < nr) {
-      const int64_t r = r0 + threadIdx.x, bt = r / C, c = r - bt * C, bb = bt / S, t = bt - bb * S;
-      if (t < len[bb]) p = x + bb * xsb + t * xss + c * K;
-    }
-    rowp[threadIdx.x] = p;
-  }
-  const int o0 = blockIdx.y * PJ_OT, oc = threadIdx.x % PJ_OT, kq = threadIdx.x / PJ_OT;
-  float acc[PJ_ROWS];
-#pragma unroll
-  for (int rr = 0; rr < PJ_ROWS; ++rr) acc[rr] = 0.f;
-  for (int k0 = 0; k0 < K; k0 += PJ_KS) {
-    const int kc = min(PJ_KS, K - k0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < PJ_ROWS * PJ_KS; i += PJ_BLOCK) {
-      const int rr = i / PJ_KS, k = i - rr * PJ_KS;
-      const float v = (rowp[rr] && k < kc) ? rowp[rr][k0 + k] : 0.f;
-      xt[rr][k] = v;
-      if (xs && blockIdx.y == 0 && rr < nr && k < kc) xs[(size_t)(r0 + rr) * K + k0 + k] = v;
-    }
-    for (int i = threadIdx.x; i < PJ_OT * PJ_KS; i += PJ_BLOCK) {
-      const int oo = i / PJ_KS, k = i - oo * PJ_KS;
-      ws[oo][k] = (o0 + oo < O && k < kc) ? W[(size_t)(o0 + oo) * K + k0 + k] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = kq * (PJ_KS / PJ_WAVES); k < (kq + 1) * (PJ_KS / PJ_WAVES); ++k) {
-      const float wv = ws[oc][k];
-#pragma unroll
-      for (int rr = 0; rr < PJ_ROWS; ++rr) acc[rr] = fmaf(xt[rr][k], wv, acc[rr]);
-    }
-  }
-#pragma unroll
-  for (int rr = 0; rr < PJ_ROWS; ++rr) red[kq][rr][oc] = acc[rr];
-  __syncthreads();
-  const int o = o0 + oc;
-  if (kq == 0 && o < O) {
-    const float bv = b[o];
-#pragma unroll
-    for (int rr = 0; rr < PJ_ROWS; ++rr)
-      if (rr < nr) gi[(size_t)(r0 + rr) * O + o] = ((red[0][rr][oc] + red[1][rr][oc]) + (red[2][rr][oc] + red[3][rr][oc])) + bv;
-  }
-}
 
 // the tile's rows: steps taken (the length clamped to [0, S]) and the stacked row (b S + 0) C + c of step 0 (step t: + t C)
 struct Tile {
@@ -432,26 +371,16 @@ int aw_check(const char* who, int64_t L0, int64_t B1, int E, int heads) {
 }
 dim3 aw_grid(int64_t L0, int64_t B1, int heads) { return dim3((unsigned)(B1 * heads), (unsigned)((L0 + AW_WAVES - 1) / AW_WAVES)); }
 
-struct Bump {
-  float* base;
-  size_t off = 0;
-  explicit Bump(void* p) : base(static_cast<float*>(p)) {}
-  float* take(size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + CG_ALIGN - 1) / CG_ALIGN * CG_ALIGN;
-    return p;
-  }
-};
 // all in (b, t, c) row order, N = B S C rows: x rows as read [N, I]; the state entering each step [N, H]; r, z, n, W_hn h + b_hn [N, 4, H]
 struct Saved { float *xs, *hp, *gates; };
-void plan_saved(Bump& b, Saved& s, size_t N, size_t I, size_t H) {
+void plan_saved(FloatBump& b, Saved& s, size_t N, size_t I, size_t H) {
   s.xs = b.take(N * I);
   s.hp = b.take(N * H);
   s.gates = b.take(N * 4 * H);
 }
 // forward: gi [N, 3H]; backward: d gi in its place and d gh [N, 3H] — one size serves both
 struct Work { float *gi, *dgh; };
-void plan_work(Bump& b, Work& w, size_t N, size_t H) {
+void plan_work(FloatBump& b, Work& w, size_t N, size_t H) {
   w.gi = b.take(N * 3 * H);
   w.dgh = b.take(N * 3 * H);
 }
@@ -476,7 +405,7 @@ extern "C" {
 
 size_t manner_hip_channel_gru_saved_bytes(int64_t B, int64_t S, int32_t C, int32_t I, int32_t H) {
   if (B <= 0 || S <= 0 || C <= 0 || I <= 0 || H <= 0) return 0;
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Saved s;
   plan_saved(b, s, (size_t)B * S * C, (size_t)I, (size_t)H);
   return b.off * sizeof(float) + 256;
@@ -484,7 +413,7 @@ size_t manner_hip_channel_gru_saved_bytes(int64_t B, int64_t S, int32_t C, int32
 
 size_t manner_hip_channel_gru_workspace_bytes(int64_t B, int64_t S, int32_t C, int32_t I, int32_t H) {
   if (B <= 0 || S <= 0 || C <= 0 || I <= 0 || H <= 0) return 0;
-  Bump b(nullptr);
+  FloatBump b(nullptr);
   Work w;
   plan_work(b, w, (size_t)B * S * C, (size_t)H);
   return b.off * sizeof(float) + 256;
@@ -502,15 +431,13 @@ int manner_hip_channel_gru_forward(const float* x, int64_t x_stride_b, int64_t x
   if (workspace_bytes < manner_hip_channel_gru_workspace_bytes(B, S, C, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "channel_gru: workspace too small");
   if (saved && saved_bytes < manner_hip_channel_gru_saved_bytes(B, S, C, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "channel_gru: saved buffer too small");
   hipStream_t s = (hipStream_t)stream;
-  Bump bw(workspace), bs(saved);
+  FloatBump bw(workspace), bs(saved);
   Work w;
   Saved sv;
   const int64_t N = B * S * C, R = B * C;
   plan_work(bw, w, (size_t)N, (size_t)H);
   plan_saved(bs, sv, (size_t)N, (size_t)I, (size_t)H);
-  hipLaunchKernelGGL(cproj_kernel, dim3((unsigned)((N + PJ_ROWS - 1) / PJ_ROWS), (unsigned)((3 * H + PJ_OT - 1) / PJ_OT)), dim3(PJ_BLOCK), 0, s, x,
-                     x_stride_b, x_stride_s, lengths, w_ih, b_ih, (int)S, (int)C, N, (int)I, 3 * H, w.gi, saved ? sv.xs : (float*)nullptr);
-  MANNER_LAUNCH_CHECK();
+  if ((rc = launch_proj_rows(x, x_stride_b, x_stride_s, lengths, w_ih, b_ih, (int)S, (int)C, N, (int)I, 3 * H, w.gi, saved ? sv.xs : nullptr, s))) return rc;
   const dim3 grid((unsigned)((R + CG_ROWS - 1) / CG_ROWS));
   if (saved)
     hipLaunchKernelGGL(cg_fwd_kernel<true>, grid, dim3(CG_BLOCK), 0, s, w.gi, w_hh, b_hh, lengths, R, (int)S, (int)C, (int)H, out, ldo, sv.hp, sv.gates,
@@ -542,7 +469,7 @@ int manner_hip_channel_gru_backward(const float* w_ih, const float* w_hh, const 
   if (saved_bytes < manner_hip_channel_gru_saved_bytes(B, S, C, I, H)) return fail(MANNER_HIP_E_WORKSPACE, "channel_gru_backward: saved buffer too small");
   if (workspace_bytes < manner_hip_channel_gru_workspace_bytes(B, S, C, I, H))
     return fail(MANNER_HIP_E_WORKSPACE, "channel_gru_backward: workspace too small");
-  Bump bw(workspace), bs(saved);
+  FloatBump bw(workspace), bs(saved);
   Work w;
   Saved sv;
   const int64_t N = B * S * C, R = B * C;

@@ -18,7 +18,6 @@ constexpr int PA_MAX_S = 256, PA_MAX_K = 64, PA_MAX_Q = 512, PA_MAX_D = 1024;
 constexpr int PA_KC = 16;        // context codes per workgroup of the forward / first backward kernel
 constexpr int PA_SB = 8;         // history rows per workgroup of the second backward kernel
 constexpr int TA_CT = 8;         // candidates per tile of the target-aware kernels
-constexpr int WG_MAX_GROUPS = 16, WG_ROWS = 64;      // weight gradient: row groups, least rows per group
 
 // N wave sums at once: the N exchange chains of a round are independent, so their cross-lane latency overlaps
 template <int N>
@@ -258,48 +257,6 @@ __global__ __launch_bounds__(256) void poly_bwd_rows_kernel(float* __restrict__ 
   }
 }
 
-// ---------------------------------------------------------------- weight gradient over many rows
-// dW[o, k] = sum_r dy[r, o] x[r, k].  grid (ceil(K / 256), O, G): group g sums its rows [g * chunk, (g + 1) * chunk) on four chains
-// into part[g][o][k] (straight into dW when G == 1); wgrad_reduce_kernel adds the G partial sums in ascending g.
-__global__ __launch_bounds__(256) void wgrad_rows_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t R, int K, int O,
-                                                         int64_t chunk, float* __restrict__ part) {
-  const int k = blockIdx.x * 256 + threadIdx.x, o = blockIdx.y;
-  if (k >= K) return;
-  const int64_t r0 = (int64_t)blockIdx.z * chunk, r1 = min(R, r0 + chunk);
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  int64_t r = r0;
-  for (; r + 3 < r1; r += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) a[u] = fmaf(dy[(r + u) * O + o], x[(r + u) * K + k], a[u]);
-  }
-  for (; r < r1; ++r) a[0] = fmaf(dy[r * O + o], x[r * K + k], a[0]);
-  part[((size_t)blockIdx.z * O + o) * K + k] = (a[0] + a[1]) + (a[2] + a[3]);
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int64_t n, int G, float* __restrict__ dW) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float s = part[i];
-  for (int g = 1; g < G; ++g) s += part[(size_t)g * n + i];
-  dW[i] = s;
-}
-
-int wgrad_groups(int64_t R) { return (int)std::max<int64_t>(1, std::min<int64_t>(WG_MAX_GROUPS, R / WG_ROWS)); }
-size_t wgrad_part_floats(int64_t R, int K, int O) { return (size_t)wgrad_groups(R) * (size_t)O * (size_t)K; }
-// R >= 1
-int launch_wgrad(const float* dy, const float* x, int64_t R, int K, int O, float* part, float* dW, hipStream_t s) {
-  const int G = wgrad_groups(R);
-  const int64_t chunk = (R + G - 1) / G;
-  hipLaunchKernelGGL(wgrad_rows_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)O, (unsigned)G), dim3(256), 0, s, dy, x, R, K, O, chunk,
-                     G == 1 ? dW : part);
-  MANNER_LAUNCH_CHECK();
-  if (G > 1) {
-    const int64_t n = (int64_t)O * K;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, n, G, dW);
-    MANNER_LAUNCH_CHECK();
-  }
-  return MANNER_HIP_OK;
-}
-
 // ---------------------------------------------------------------- TargetAwareAttention
 // The mixture weights of the candidates [c0, c0 + nc) of user b: lg[cc][k] = key[b, c, :] . proj[k, :], proj = gelu(pre) (GELU
 // true: pre holds the Linear output, gelu applied here) or pre itself (GELU false: the caller has applied it).  Wave w takes the codes
@@ -526,7 +483,7 @@ int manner_hip_poly_attention(const float* x, const uint8_t* mask, const float* 
 size_t manner_hip_poly_attention_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t Q, int32_t K) {
   if (B <= 0 || S <= 0 || D <= 0 || Q <= 0 || K <= 0) return 0;
   const size_t R = (size_t)(B * S);
-  const size_t part = std::max(wgrad_part_floats(B * S, D, Q), wgrad_part_floats(B * S, Q, K));
+  const size_t part = std::max(wgrad_rows_part_floats(B * S, D, Q), wgrad_rows_part_floats(B * S, Q, K));
   return (R * (size_t)(2 * Q + D + 2 * K) + part) * sizeof(float) + 256;
 }
 
@@ -559,8 +516,8 @@ int manner_hip_poly_attention_backward(const float* x, const uint8_t* mask, cons
   hipLaunchKernelGGL(poly_bwd_rows_kernel, dim3((unsigned)B, (unsigned)((S + PA_SB - 1) / PA_SB)), dim3(256), 0, s, pre, codes, grad_out, p, dl, (int)S,
                      D, Q, K, act, add);
   MANNER_LAUNCH_CHECK();
-  if ((rc = launch_wgrad(dl, act, R, Q, K, part, grad_codes, s))) return rc;
-  if ((rc = launch_wgrad(pre, x, R, D, Q, part, grad_w, s))) return rc;
+  if ((rc = launch_wgrad_rows(dl, K, act, R, Q, K, part, grad_codes, Q, s))) return rc;
+  if ((rc = launch_wgrad_rows(pre, Q, x, R, D, Q, part, grad_w, D, s))) return rc;
   return manner_hip_linear_backward(x, lin_w, pre, R, D, Q, add, grad_x, nullptr, nullptr, stream);
 }
 
@@ -586,7 +543,7 @@ int manner_hip_target_attention(const float* query, const float* key, const floa
 
 size_t manner_hip_target_attention_backward_workspace_bytes(int64_t B, int32_t K, int32_t D) {
   if (B <= 0 || K <= 0 || D <= 0) return 0;
-  return ((size_t)(B * K) * (size_t)D * 3 + wgrad_part_floats(B * K, D, D)) * sizeof(float) + 256;
+  return ((size_t)(B * K) * (size_t)D * 3 + wgrad_rows_part_floats(B * K, D, D)) * sizeof(float) + 256;
 }
 
 int manner_hip_target_attention_backward(const float* query, const float* key, const float* value, const float* lin_w, const float* grad_out,
@@ -613,7 +570,7 @@ int manner_hip_target_attention_backward(const float* query, const float* key, c
   if ((rc = manner_hip_linear(query, lin_w, nullptr, R, D, D, pre, stream))) return rc;
   hipLaunchKernelGGL(target_bwd_kernel, dim3((unsigned)B), dim3(256), 0, s, pre, key, value, grad_out, C, K, D, proj, dpre, grad_key, grad_value);
   MANNER_LAUNCH_CHECK();
-  if ((rc = launch_wgrad(dpre, query, R, D, D, part, grad_w, s))) return rc;
+  if ((rc = launch_wgrad_rows(dpre, D, query, R, D, D, part, grad_w, D, s))) return rc;
   return manner_hip_linear_backward(query, lin_w, dpre, R, D, D, nullptr, grad_query, nullptr, nullptr, stream);
 }
 

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void gather_cls_kernel(const TIn* __restrict__
 
 // compact copy of the [CLS] rows, same dtype: dst[n] = x[cu[n]]
 template <typename T>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ x, const int32_t* __restrict__ cu,
+__global__ __launch_bounds__(256) void gather_cls_rows_kernel(const T* __restrict__ x, const int32_t* __restrict__ cu,
                                                           int H, T* __restrict__ dst) {
   const int64_t n = blockIdx.x;
   const f32x4* src = reinterpret_cast<const f32x4*>(x + (size_t)cu[n] * H);
@@ -548,9 +548,9 @@ int gather_cls(DType in, const void* x, const int32_t* cu, int64_t n_news, int H
 int gather_cls_rows(DType dt, const void* x, const int32_t* cu, int64_t n_news, int H, void* dst, hipStream_t stream) {
   dim3 g((unsigned)n_news), b(256);
   if (is_16bit(dt))      // a 2-byte row copy: one instantiation serves bf16 and f16
-    hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, g, b, 0, stream, static_cast<const bf16_t*>(x), cu, H, static_cast<bf16_t*>(dst));
+    hipLaunchKernelGGL(gather_cls_rows_kernel<bf16_t>, g, b, 0, stream, static_cast<const bf16_t*>(x), cu, H, static_cast<bf16_t*>(dst));
   else
-    hipLaunchKernelGGL(gather_rows_kernel<float>, g, b, 0, stream, static_cast<const float*>(x), cu, H, static_cast<float*>(dst));
+    hipLaunchKernelGGL(gather_cls_rows_kernel<float>, g, b, 0, stream, static_cast<const float*>(x), cu, H, static_cast<float*>(dst));
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }

@@ -5,19 +5,12 @@
 // Composed into autograd Functions by manner_amd/train.py.
 #include <math.h>
 
-#include "common.h"
+#include "train_common.h"
 
 namespace manner {
 namespace {
 
-// same generator as train.hip (splitmix64 of (seed, site, index)); kept when bits >= thr
-__device__ __forceinline__ uint32_t drop_bits(uint64_t seed, uint32_t site, uint64_t idx) {
-  uint64_t z = (seed ^ ((uint64_t)site * 0xD6E8FEB86659FD93ull)) + (idx + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(z >> 32);
-}
+// dropout bits: train_common.h's generator (splitmix64 of (seed, site, index)); kept when bits >= thr
 __global__ __launch_bounds__(256) void dropout_flat_kernel(const float* x, float* out, int64_t n, uint64_t seed, uint32_t site,
                                                            uint32_t thr, float scale) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -72,39 +65,6 @@ __global__ __launch_bounds__(256) void lin_bwd_w_kernel(const float* __restrict_
   }
   if (r < R) a0 = fmaf(dy[r * O + o], x[r * K + k], a0);
   dW[(size_t)o * K + k] = a0 + a1;
-}
-// db[o] = sum_r dy[r, o].  A workgroup owns 64 columns and splits the rows over 16 groups of four accumulators each; the 64 partial
-// sums of a column meet in LDS and are added pairwise, in a fixed order.  (One thread used to walk all R rows of its column with a
-// single f32 accumulator: over the 771 .. 900 rows of the axis-0 attention tests that bias gradient sat 11 - 13 x further from
-// float64 than a float32 CPU sum, past the 8 x bar of tests/test_gpu_side_ops.py, and every thread waited on R dependent loads.)
-constexpr int CS_COLS = 64, CS_GROUPS = 16;
-__global__ __launch_bounds__(CS_COLS * CS_GROUPS) void colsum_small_kernel(const float* __restrict__ dy, int64_t R, int O,
-                                                                            float* __restrict__ db) {
-  __shared__ float red[CS_GROUPS][CS_COLS];
-  const int col = threadIdx.x % CS_COLS, g = threadIdx.x / CS_COLS;
-  const int o = blockIdx.x * CS_COLS + col;
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  if (o < O) {
-    int64_t r = g;
-    for (; r + 3 * CS_GROUPS < R; r += 4 * CS_GROUPS) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] += dy[(r + u * CS_GROUPS) * O + o];
-    }
-    for (; r < R; r += CS_GROUPS) s[0] += dy[r * O + o];
-  }
-  red[g][col] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  if (g == 0 && o < O) {
-    float t[CS_GROUPS];
-#pragma unroll
-    for (int i = 0; i < CS_GROUPS; ++i) t[i] = red[i][col];
-#pragma unroll
-    for (int w = CS_GROUPS / 2; w > 0; w >>= 1) {
-#pragma unroll
-      for (int i = 0; i < w; ++i) t[i] += t[i + w];
-    }
-    db[o] = t[0];
-  }
 }
 
 // ---------------------------------------------------------------- AdditiveAttention backward (attention.py:21-27)
@@ -234,11 +194,7 @@ int manner_hip_linear_backward(const float* x, const float* weight, const float*
     hipLaunchKernelGGL(lin_bwd_w_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)O), dim3(256), 0, s, grad_y, x, R, K, O, grad_w);
     MANNER_LAUNCH_CHECK();
   }
-  if (grad_b) {
-    hipLaunchKernelGGL(colsum_small_kernel, dim3((unsigned)((O + CS_COLS - 1) / CS_COLS)), dim3(CS_COLS * CS_GROUPS), 0, s, grad_y, R, O, grad_b);
-    MANNER_LAUNCH_CHECK();
-  }
-  return MANNER_HIP_OK;
+  return grad_b ? launch_colsum_rows(grad_y, O, R, O, grad_b, s) : MANNER_HIP_OK;
 }
 
 size_t manner_hip_additive_pool_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t Q) {

@@ -330,7 +330,7 @@ def linear_terms(x, weight, bias, dy, absolute=False, dtype=np.float64):
     return out
 
 
-LINEAR_SHAPES = ((1, 4, 1), (9, 8, 2049), (9, 8, 4100), (17, 257, 300), (8, 512, 5), (7, 2049, 3), (9, 4096, 5))
+LINEAR_SHAPES = ((1, 4, 1), (9, 8, 2049), (9, 8, 4100), (17, 257, 300), (8, 512, 5), (7, 2049, 3), (9, 4096, 5), (65, 8, 70))
 
 
 @functools.lru_cache(maxsize=None)

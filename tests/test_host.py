@@ -898,3 +898,23 @@ def test_generated_gemm_asm_is_in_sync_with_its_generator(tmp_path):
         assert (tmp_path / n).read_text(encoding="utf-8") == text, f"{n} differs from what its generator in tools/ writes"
     # and the schedule's own invariants: every K-step body has 64 matrix instructions per wave (8-wave form), the LDS-queue simulation ran
     assert committed["gemm_w8_asm.inc"].count('MFMA "') == 2 * 4 * 64 and committed["gemm_w4_asm.inc"].count('MFMA "') == 4 * 128
+
+
+def test_every_kernel_name_is_defined_in_one_file():
+    """Kernel traces (rocprofv3, profiles/*/kernel_trace.json) identify a kernel by its name: two kernels under one name in different
+    files of csrc/ make such a trace ambiguous, and are usually two copies of one kernel.  A shared kernel lives in one file (a header
+    for a template that each caller instantiates)."""
+    import glob
+    import re
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(ROOT, "manner_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 20
+    where = {}
+    for path in files:
+        text = open(path, encoding="utf-8").read()
+        for name in re.findall(r"__global__\b[^;{]*?\bvoid\s+(\w+)\s*\(", text, flags=re.S):
+            where.setdefault(name, set()).add(os.path.basename(path))
+    assert len(where) >= 100, "the pattern no longer finds the kernels"
+    shared = {name: sorted(fs) for name, fs in where.items() if len(fs) > 1}
+    assert not shared, f"kernel names defined in more than one file: {shared}"
