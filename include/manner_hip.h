@@ -428,6 +428,42 @@ int manner_hip_gather_segments(const int32_t* src, const float* src_f, const int
 int manner_hip_rows_max_len(const int32_t* store_len, const int32_t* store_cnt, int64_t n_news, const int32_t* rows, int64_t M,
                             int32_t* out_max, manner_hip_stream_t stream);
 
+/* ---------------------------------------------------------------- A-Module batches: M-per-class sampling on the device
+ * Replaces pytorch_metric_learning's MPerClassSampler as MINDNewsDataModule uses it — manner/data/mind_news_datamodule.py:175-217,
+ * MPerClassSampler(labels, m, batch_size, length_before_new_iter=len(data_train)) — in front of the collate_* kernels: a whole
+ * epoch of news batches in one call.  The data set is N news with one aspect label each; the distinct labels in ascending value
+ * are the classes 0..L-1 (class_label int64 [L]), class l has n_l = class_off[l+1] - class_off[l] members, and
+ * class_members int32 [N] lists the data-set indices grouped by class, ascending inside a class (class_off int64 [L+1]);
+ * rows int32 [N] maps a data-set index to its row of the news store.
+ *
+ * The sampling rule (documented behaviour of MPerClassSampler, not its random stream).  An epoch is nb batches of
+ * B = k * m slots: k distinct classes chosen uniformly afresh for every batch, in random order, each filling a block of m
+ * consecutive slots with m distinct members drawn uniformly — or, where the class has fewer than m members, with m draws with
+ * replacement.  With key() of "training batches" above, its third argument now the batch or the unit, and two streams of its own:
+ *   class choice of batch b: the k classes with the smallest (key(seed, epoch, b, 16, l), l), in that order;
+ *   block j of batch b has unit = b * k + j, draws from its class of n members, h_t = key(seed, epoch, unit, 17, t) >> 32:
+ *     n >= m (Floyd's subset algorithm): for t = 0..m-1: J = n - m + t, r = (h_t * (J + 1)) >> 32; append J if r was appended
+ *             before, else r;
+ *     n <  m: draw t is (h_t * n) >> 32;
+ *   the block lists the drawn members in draw order.  That order is not a uniform permutation of the subset (Floyd's J can only
+ *   appear at or after step t) and need not be: the supervised contrastive loss, the batch-coupled entity attention and the
+ *   iid dropouts are equivariant to the order inside a batch.
+ * A sample is a pure function of (seed, epoch, b, j) and the label array: no atomics, no stored keys, no dependence on the
+ * launch geometry.
+ *
+ *   sample_m_per_class: out_idx int32 [nb * B] data-set indices, out_rows int32 [nb * B] their store rows, out_labels int64
+ *                       [nb * B], out_width int32 [nb, 2] = per batch the longest stored token row and the longest entity list
+ *                       among its rows (the padding=True widths; store_cnt == NULL: 0).  Bounds: 1 <= m <= 256,
+ *                       1 <= k <= L <= 1024, 1 <= N < 2^31, nb * k * m < 2^31 — anything else is MANNER_HIP_E_INVALID before
+ *                       any launch.  A rows entry outside [0, n_news), a member outside [0, N) or a class without members raises
+ *                       MANNER_HIP_STATUS_INDEX in *status (device int32, may be NULL); the slot is then written with the index
+ *                       clamped into its table. */
+int manner_hip_sample_m_per_class(const int64_t* class_off, const int32_t* class_members, const int64_t* class_label, int32_t L,
+                                  int64_t N, const int32_t* rows, const int32_t* store_len, const int32_t* store_cnt, int64_t n_news,
+                                  int32_t m, int32_t k, int64_t nb, uint64_t seed, uint64_t epoch, int32_t* out_idx,
+                                  int32_t* out_rows, int64_t* out_labels, int32_t* out_width, int32_t* status,
+                                  manner_hip_stream_t stream);
+
 /* ---------------------------------------------------------------- evaluation loss (val/loss, test/loss)
  * Replaces the loss of CRModule.model_step — manner/models/cr_module.py:140-171, run by validation_step and test_step
  * (:211-262) on every batch — per impression, on the ragged scores (no dense [B, Cmax] matrix, no host loops).
@@ -476,8 +512,9 @@ int manner_hip_eval_loss(const float* scores, const float* labels, const int64_t
  * d loss / d parameter.  The activation gradient travels as far down as a requested gradient needs — through frozen
  * layers into the embedding tables when an embedding tensor is trainable, which is the reference's default
  * (news_encoder.py:24-27 freezes "layer.N." parameters only).  grad_prefix (optional, start_layer > 0): f32
- * [n_news, padded_len, H] gradient of prefix_hidden.  Embedding-table gradients use f32 atomics (summation order, hence
- * the last bits, vary between runs — as torch's CUDA embedding backward). */
+ * [n_news, padded_len, H] gradient of prefix_hidden.  Embedding-table gradients: up to 8192 padded positions (n_news * padded_len — an
+ * A-Module step) every table row is summed by one workgroup in position order, the same bits on every run; larger batches use f32
+ * atomics (summation order, hence the last bits, vary between runs — as torch's CUDA embedding backward). */
 size_t manner_hip_train_saved_bytes(const manner_hip_encoder_config* cfg, int64_t n_news, int64_t m_bound, int32_t start_layer);
 size_t manner_hip_train_workspace_bytes(const manner_hip_encoder_config* cfg, int64_t m_bound);
 /* ABI v7 — the bytes manner_hip_train_forward needs for `saved` IN THE GIVEN PRECISION (never more than the function above, which
@@ -586,7 +623,8 @@ int manner_hip_supcon_embeddings(const float* emb, const int64_t* labels, int64_
  *    calls it (quirk Q1: along axis 0 of [L0, B1, E], per position B1 and head, no mask, no attention dropout) on projected
  *    qkv [L0, B1, 3E] = [q | k | v]; backward: grad_qkv [L0, B1, 3E] from grad_out [L0, B1, E], stats = L0*B1*heads*3 floats of scratch;
  *  - manner_hip_embedding(_backward): nn.Embedding.from_pretrained(..., freeze=False, padding_idx=0) (news_encoder.py:99-103):
- *    lookup, and grad_table [n_rows, D] (overwritten; row padding_idx receives no gradient; f32 atomics);
+ *    lookup, and grad_table [n_rows, D] (overwritten; row padding_idx receives no gradient; up to 8192 ids each row is summed in id
+ *    order by one workgroup, the same bits on every run; more ids use f32 atomics);
  *  - manner_hip_dropout: out = keep ? x / (1 - p) : 0 over a flat tensor with the training path's generator (its own
  *    backward: apply it to the gradient with the same seed / site). */
 int manner_hip_linear_backward(const float* x, const float* weight, const float* grad_y, int64_t R, int32_t K, int32_t O,

@@ -119,6 +119,8 @@ SIGNATURES = {
                                                _P, _P, _P]),
     "manner_hip_gather_segments": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P]),
     "manner_hip_rows_max_len": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "manner_hip_sample_m_per_class": (C.c_int, [_P, _P, _P, _I32, _I64, _P, _P, _P, _I64, _I32, _I32, _I64, C.c_uint64, C.c_uint64, _P, _P,
+                                                _P, _P, _P, _P]),
     "manner_hip_poly_attention_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),
     "manner_hip_poly_attention": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _SZ, _P]),
     "manner_hip_poly_attention_backward_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),

@@ -311,6 +311,119 @@ __global__ __launch_bounds__(256) void rows_max_len_kernel(const int32_t* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------ A-Module batches
+// MPerClassSampler as MINDNewsDataModule uses it (manner/data/mind_news_datamodule.py:175-217) as a counter-based rule (stated in
+// include/manner_hip.h, "A-Module batches"): a whole epoch in one launch, one wave per block (b, j) of m slots.  The class choice is
+// a rank count over the L keys of batch b (each wave of the batch recounts it: L <= 1024 keys in LDS); Floyd's subset algorithm keeps
+// the drawn set spread over the lanes, draw t in lane t & 63, register t >> 6, and its membership test is one wave-wide compare a step.
+constexpr int MPC_MAX_M = 256, MPC_MAX_L = 1024;
+
+__global__ __launch_bounds__(256) void m_per_class_kernel(const int64_t* __restrict__ class_off, const int32_t* __restrict__ class_members,
+                                                         const int64_t* __restrict__ class_label, int L, int64_t N,
+                                                         const int32_t* __restrict__ rows, int64_t n_news, int m, int k, int64_t units,
+                                                         uint64_t seed_epoch, int32_t* __restrict__ out_idx, int32_t* __restrict__ out_rows,
+                                                         int64_t* __restrict__ out_labels, int32_t* __restrict__ status) {
+  __shared__ uint64_t s_key[4][MPC_MAX_L];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t unit_raw = blockIdx.x * 4ll + wave;
+  const bool active = unit_raw < units;
+  const int64_t unit = active ? unit_raw : units - 1;     // an idle wave of the last workgroup recounts the last unit and writes nothing
+  const int64_t b = unit / k;
+  const int j = (int)(unit - b * k);
+
+  uint64_t* keys = s_key[wave];
+  const uint64_t base_b = mix64(seed_epoch ^ (uint64_t)b);
+  for (int l = lane; l < L; l += 64) keys[l] = slot_key(base_b, 16, l);
+  __syncthreads();
+  int cls = -1;                                           // the class of rank j by (key, l): the ranks are a permutation, so one lane hits
+  for (int c0 = 0; c0 < L; c0 += 64) {
+    const int l = c0 + lane;
+    int r = -1;
+    if (l < L) {
+      const uint64_t kl = keys[l];
+      r = 0;
+      for (int i = 0; i < L; ++i) {
+        const uint64_t ki = keys[i];
+        r += (ki < kl) || (ki == kl && i < l);
+      }
+    }
+    const unsigned long long hit = __ballot(r == j);
+    if (hit) cls = c0 + __builtin_ctzll(hit);
+  }
+  if (!active || cls < 0) return;                         // (no barrier below)
+
+  const int64_t o0 = class_off[cls], o1 = class_off[cls + 1];
+  const int64_t label = class_label[cls];
+  const int64_t out0 = unit * m;
+  if (o0 < 0 || o1 > N || o1 <= o0) {                     // a class without members, or offsets that leave class_members
+    for (int t = lane; t < m; t += 64) { out_idx[out0 + t] = 0; out_rows[out0 + t] = 0; out_labels[out0 + t] = label; }
+    if (lane == 0 && status) atomicOr(status, MANNER_HIP_STATUS_INDEX);
+    return;
+  }
+  const int n = (int)(o1 - o0);                           // N < 2^31
+
+  const uint64_t base_u = mix64(seed_epoch ^ (uint64_t)unit);
+  uint32_t h[4];
+  int d[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    h[s] = (uint32_t)(slot_key(base_u, 17, s * 64 + lane) >> 32);
+    d[s] = -1;
+  }
+  if (n >= m) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int lim = m - s * 64 < 64 ? m - s * 64 : 64;
+      for (int i = 0; i < lim; ++i) {
+        const uint32_t ht = (uint32_t)__shfl((int)h[s], i, 64);
+        const int J = n - m + s * 64 + i;
+        const int r = (int)(((uint64_t)ht * (uint64_t)(J + 1)) >> 32);
+        const bool seen = d[0] == r || d[1] == r || d[2] == r || d[3] == r;
+        const int v = __ballot(seen) ? J : r;
+        if (lane == i) d[s] = v;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) d[s] = (int)(((uint64_t)h[s] * (uint64_t)n) >> 32);
+  }
+
+  int flag = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int t = s * 64 + lane;
+    if (t < m) {                                          // 0 <= d[s] < n, so the read of class_members is inside [o0, o1)
+      int64_t idx = class_members[o0 + d[s]];
+      if (idx < 0 || idx >= N) { flag = MANNER_HIP_STATUS_INDEX; idx = idx < 0 ? 0 : N - 1; }
+      int64_t row = rows[idx];
+      if (row < 0 || row >= n_news) { flag = MANNER_HIP_STATUS_INDEX; row = row < 0 ? 0 : n_news - 1; }
+      out_idx[out0 + t] = (int32_t)idx;
+      out_rows[out0 + t] = (int32_t)row;
+      out_labels[out0 + t] = label;
+    }
+  }
+  if (flag && status) atomicOr(status, flag);
+}
+
+// The padding=True widths of every batch of the epoch: one wave per batch over the store rows the launch above wrote.
+__global__ __launch_bounds__(256) void batch_width_kernel(const int32_t* __restrict__ store_len, const int32_t* __restrict__ store_cnt,
+                                                         int64_t n_news, const int32_t* __restrict__ batch_rows, int64_t B, int64_t nb,
+                                                         int32_t* __restrict__ out_width) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = blockIdx.x * 4ll + (threadIdx.x >> 6);
+  if (b >= nb) return;
+  const int32_t* r = batch_rows + b * B;
+  int ml = 0, mc = 0;
+  for (int64_t i = lane; i < B; i += 64) {
+    int64_t src = r[i];
+    src = src < 0 ? 0 : (src >= n_news ? n_news - 1 : src);
+    ml = max(ml, store_len[src]);
+    if (store_cnt) mc = max(mc, store_cnt[src]);
+  }
+  for (int o = 32; o > 0; o >>= 1) { ml = max(ml, __shfl_xor(ml, o, 64)); mc = max(mc, __shfl_xor(mc, o, 64)); }
+  if (lane == 0) { out_width[2 * b] = ml; out_width[2 * b + 1] = mc; }
+}
+
 unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
 
 }  // namespace
@@ -400,6 +513,31 @@ int manner_hip_rows_max_len(const int32_t* store_len, const int32_t* store_cnt, 
   if (!out_max || M < 0 || (M && (!store_len || !rows || n_news <= 0)))
     return fail(MANNER_HIP_E_INVALID, "rows_max_len: bad argument");
   hipLaunchKernelGGL(rows_max_len_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, store_len, store_cnt, n_news, rows, M, out_max);
+  MANNER_LAUNCH_CHECK();
+  return MANNER_HIP_OK;
+}
+
+int manner_hip_sample_m_per_class(const int64_t* class_off, const int32_t* class_members, const int64_t* class_label, int32_t L,
+                                  int64_t N, const int32_t* rows, const int32_t* store_len, const int32_t* store_cnt, int64_t n_news,
+                                  int32_t m, int32_t k, int64_t nb, uint64_t seed, uint64_t epoch, int32_t* out_idx,
+                                  int32_t* out_rows, int64_t* out_labels, int32_t* out_width, int32_t* status,
+                                  manner_hip_stream_t stream) {
+  if (m < 1 || m > MPC_MAX_M) return fail(MANNER_HIP_E_INVALID, "sample_m_per_class: m = %d outside [1, %d]", (int)m, MPC_MAX_M);
+  if (L < 1 || L > MPC_MAX_L) return fail(MANNER_HIP_E_INVALID, "sample_m_per_class: L = %d outside [1, %d]", (int)L, MPC_MAX_L);
+  if (k < 1 || k > L) return fail(MANNER_HIP_E_INVALID, "sample_m_per_class: k = %d outside [1, L = %d]", (int)k, (int)L);
+  if (N < 1 || N > 0x7fffffff || n_news < 1 || nb < 0) return fail(MANNER_HIP_E_INVALID, "sample_m_per_class: bad argument");
+  const int64_t B = (int64_t)k * m;                       // <= 2^18 after the checks above
+  if (nb > 0x7fffffff / B) return fail(MANNER_HIP_E_INVALID, "sample_m_per_class: nb * k * m overflows 2^31");
+  if (nb == 0) return MANNER_HIP_OK;
+  if (!class_off || !class_members || !class_label || !rows || !store_len || !out_idx || !out_rows || !out_labels || !out_width)
+    return fail(MANNER_HIP_E_INVALID, "sample_m_per_class: null argument");
+  const int64_t units = nb * k;
+  const uint64_t seed_epoch = mix64(seed + 0x9E3779B97F4A7C15ull * (epoch + 1));
+  hipLaunchKernelGGL(m_per_class_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, class_off, class_members,
+                     class_label, (int)L, N, rows, n_news, (int)m, (int)k, units, seed_epoch, out_idx, out_rows, out_labels, status);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(batch_width_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, (hipStream_t)stream, store_len, store_cnt, n_news,
+                     out_rows, B, nb, out_width);
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }

@@ -106,6 +106,76 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restric
   }
 }
 
+// The same sums without atomics, for batches small enough that one scan of the positions per row costs nothing (an A-Module step is 60
+// news): the first position that holds a word id (blockIdx.y == 0) or a position row (blockIdx.y == 1) adds up every position holding
+// it, in position order — one writer per table row, so these two gradients are the same bits on every run.
+constexpr int64_t EMBED_ORDERED_MAX = 8192;
+// the table row position j = n * lp + t adds to, or -1 (padding, or a row that takes no gradient); as embed_bwd_kernel places them
+__device__ __forceinline__ int embed_bwd_key(int j, bool pos_side, const int64_t* __restrict__ ids, int lp, const int32_t* __restrict__ cu,
+                                             int pos_offset, int vocab, int max_pos, const int32_t* __restrict__ klen, int pad_pos,
+                                             int word_pad, int pos_pad) {
+  const int n = j / lp, t = j - n * lp;
+  if (t >= cu[n + 1] - cu[n]) return -1;
+  if (!pos_side) {
+    int64_t id = ids[j];
+    if (id < 0 || id >= vocab) id = 0;
+    return id == word_pad ? -1 : (int)id;
+  }
+  int p = t + pos_offset;
+  if (klen && pad_pos >= 0 && t >= klen[n]) p = pad_pos;
+  if (p >= max_pos) p = max_pos - 1;
+  return p == pos_pad ? -1 : p;
+}
+__global__ __launch_bounds__(256) void embed_bwd_ordered_kernel(const int64_t* __restrict__ ids, int total, int lp,
+                                                                const int32_t* __restrict__ cu, const float* __restrict__ de, int H,
+                                                                int pos_offset, int vocab, int max_pos, float* __restrict__ dword,
+                                                                float* __restrict__ dpos, const int32_t* __restrict__ klen, int pad_pos,
+                                                                int word_pad, int pos_pad) {
+  __shared__ unsigned long long s_mask[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool pos_side = blockIdx.y == 1;
+  float* table = pos_side ? dpos : dword;
+  if (!table) return;
+  const int i = blockIdx.x;
+#define EMBED_KEY(j) embed_bwd_key(j, pos_side, ids, lp, cu, pos_offset, vocab, max_pos, klen, pad_pos, word_pad, pos_pad)
+  const int k = EMBED_KEY(i);
+  if (k < 0) return;                                             // (the whole workgroup)
+  int seen = 0;
+  for (int j = tid; j < i; j += 256) seen |= EMBED_KEY(j) == k;
+  if (__syncthreads_or(seen)) return;
+  float* dst = table + (size_t)k * H;
+  for (int c0 = 0; c0 < H; c0 += 1024) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int j0 = i; j0 < total; j0 += 256) {
+      const int j = j0 + tid;
+      const unsigned long long m = __ballot(j < total && EMBED_KEY(j) == k);
+      if (lane == 0) s_mask[wave] = m;
+      __syncthreads();
+      for (int w = 0; w < 4; ++w) {
+        unsigned long long mm = s_mask[w];
+        while (mm) {
+          const int jj = j0 + w * 64 + __builtin_ctzll(mm);
+          mm &= mm - 1;
+          const int n = jj / lp;
+          const float* src = de + (size_t)(cu[n] + (jj - n * lp)) * H;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c = c0 + q * 256 + tid;
+            if (c < H) acc[q] += src[c];
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int c = c0 + q * 256 + tid;
+      if (c < H) dst[c] = acc[q];
+    }
+  }
+#undef EMBED_KEY
+}
+
 // x[cu[n]+t] = hidden[n, t]  (cached frozen-prefix activations, [N, Lp, H] f32 -> packed rows) and its inverse for the
 // gradient of the prefix
 __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ padded, float* __restrict__ packed,
@@ -2085,7 +2155,13 @@ static int train_backward_impl(const manner_hip_encoder_config* cfg, const float
     const int pos_offset = cfg->arch == MANNER_HIP_ARCH_ROBERTA ? cfg->pad_id + 1 : 0;
     if (gemb(MANNER_HIP_W_WORD_EMB)) MANNER_HIP_TRY(hipMemsetAsync(gemb(MANNER_HIP_W_WORD_EMB), 0, (size_t)cfg->vocab * H * sizeof(float), s));
     if (gemb(MANNER_HIP_W_POS_EMB)) MANNER_HIP_TRY(hipMemsetAsync(gemb(MANNER_HIP_W_POS_EMB), 0, (size_t)cfg->max_pos * H * sizeof(float), s));
-    if (gemb(MANNER_HIP_W_WORD_EMB) || gemb(MANNER_HIP_W_POS_EMB)) {
+    if ((gemb(MANNER_HIP_W_WORD_EMB) || gemb(MANNER_HIP_W_POS_EMB)) && n_news * padded_len <= EMBED_ORDERED_MAX) {
+      hipLaunchKernelGGL(embed_bwd_ordered_kernel, dim3(tok_blocks, 2), dim3(256), 0, s, ids, (int)tok_blocks, (int)padded_len, sv.cu, wk.dr,
+                         H, pos_offset, cfg->vocab, cfg->max_pos, gemb(MANNER_HIP_W_WORD_EMB), gemb(MANNER_HIP_W_POS_EMB),
+                         full ? sv.lens : nullptr, (full && cfg->arch == MANNER_HIP_ARCH_ROBERTA) ? cfg->pad_id : -1, cfg->pad_id,
+                         cfg->arch == MANNER_HIP_ARCH_ROBERTA ? cfg->pad_id : -1);
+      MANNER_LAUNCH_CHECK();
+    } else if (gemb(MANNER_HIP_W_WORD_EMB) || gemb(MANNER_HIP_W_POS_EMB)) {
       hipLaunchKernelGGL(embed_bwd_kernel, dim3(tok_blocks), dim3(256), 0, s, ids, n_news, (int)padded_len, sv.cu, wk.dr, H, pos_offset,
                          cfg->vocab, cfg->max_pos, gemb(MANNER_HIP_W_WORD_EMB), gemb(MANNER_HIP_W_POS_EMB), full ? sv.lens : nullptr,
                          (full && cfg->arch == MANNER_HIP_ARCH_ROBERTA) ? cfg->pad_id : -1, cfg->pad_id,

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void lin_bwd_w_kernel(const float* __restrict_
 constexpr int POOL_MAX_S = 1024;
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ x, float* __restrict__ pre, const float* __restrict__ query,
                                                        const float* __restrict__ dout, int S, int D, int Q, float* __restrict__ wout,
-                                                       float* __restrict__ dq) {
+                                                       float* __restrict__ dq_part) {
   __shared__ float lg[POOL_MAX_S], dw[POOL_MAX_S];
   __shared__ float red[4];
   const int64_t b = blockIdx.x;
@@ -127,8 +127,16 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
       acc = fmaf(dw[s], a, acc);
       pb[(size_t)s * Q + j] = dw[s] * qj * (1.f - a * a);
     }
-    atomicAdd(dq + j, acc);
+    dq_part[b * Q + j] = acc;
   }
+}
+// dq[j] = sum_b dq_part[b, j], in row order: the same bits on every run (f32 atomics across the rows were not)
+__global__ __launch_bounds__(256) void pool_dq_kernel(const float* __restrict__ dq_part, int64_t B, int Q, float* __restrict__ dq) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= Q) return;
+  float acc = 0.f;
+  for (int64_t b = 0; b < B; ++b) acc += dq_part[b * Q + j];
+  dq[j] = acc;
 }
 // add[b, s, :] = w[b, s] * dout[b, :]
 __global__ __launch_bounds__(256) void pool_wdout_kernel(const float* __restrict__ w, const float* __restrict__ dout, int64_t R, int S,
@@ -154,6 +162,48 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
   const int64_t id = ids[r];
   if (id < 0 || id >= n_rows || id == padding_idx) return;
   for (int c = threadIdx.x; c < D; c += 256) atomicAdd(dtable + id * D + c, dy[r * D + c]);
+}
+// The same sums without atomics, for batches small enough that one scan of the ids per row costs nothing (an A-Module step has a few
+// hundred entity slots): the first row that holds an id adds up every row holding it, in row order — one writer per table row, so
+// the gradient is the same bits on every run.
+constexpr int64_t EMBEDDING_ORDERED_MAX = 8192;
+__global__ __launch_bounds__(256) void embedding_bwd_ordered_kernel(const int64_t* __restrict__ ids, const float* __restrict__ dy, int R,
+                                                                    int64_t n_rows, int D, int64_t padding_idx, float* __restrict__ dtable) {
+  __shared__ unsigned long long s_mask[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = blockIdx.x;
+  const int64_t id = ids[r];
+  if (id < 0 || id >= n_rows || id == padding_idx) return;        // (the whole workgroup)
+  int seen = 0;
+  for (int j = tid; j < r; j += 256) seen |= ids[j] == id;
+  if (__syncthreads_or(seen)) return;
+  for (int c0 = 0; c0 < D; c0 += 1024) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int j0 = r; j0 < R; j0 += 256) {
+      const int j = j0 + tid;
+      const unsigned long long m = __ballot(j < R && ids[j] == id);
+      if (lane == 0) s_mask[wave] = m;
+      __syncthreads();
+      for (int w = 0; w < 4; ++w) {
+        unsigned long long mm = s_mask[w];
+        while (mm) {
+          const float* src = dy + (size_t)(j0 + w * 64 + __builtin_ctzll(mm)) * D;
+          mm &= mm - 1;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c = c0 + q * 256 + tid;
+            if (c < D) acc[q] += src[c];
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int c = c0 + q * 256 + tid;
+      if (c < D) dtable[id * D + c] = acc[q];
+    }
+  }
 }
 
 }  // namespace
@@ -199,7 +249,7 @@ int manner_hip_linear_backward(const float* x, const float* weight, const float*
 
 size_t manner_hip_additive_pool_backward_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t Q) {
   if (B <= 0 || S <= 0 || D <= 0 || Q <= 0) return 0;
-  return (size_t)(B * S) * (size_t)(Q + D + 1) * sizeof(float) + 1024;
+  return ((size_t)(B * S) * (size_t)(Q + D + 1) + (size_t)B * Q) * sizeof(float) + 1024;
 }
 
 int manner_hip_additive_pool_backward(const float* x, const float* lin_w, const float* lin_b, const float* query, const float* grad_out,
@@ -223,10 +273,12 @@ int manner_hip_additive_pool_backward(const float* x, const float* lin_w, const 
   float* pre = static_cast<float*>(workspace);          // [R, Q]: pre-activations, then d pre
   float* add = pre + (size_t)R * Q;                     // [R, D]: w_s * dout
   float* w = add + (size_t)R * D;                       // [R]
+  float* dq_part = w + R;                               // [B, Q]: each row's share of d query, summed in row order below
   int rc;
   if ((rc = manner_hip_linear(x, lin_w, lin_b, R, D, Q, pre, stream))) return rc;
-  MANNER_HIP_TRY(hipMemsetAsync(grad_q, 0, (size_t)Q * sizeof(float), s));
-  hipLaunchKernelGGL(pool_bwd_kernel, dim3((unsigned)B), dim3(256), 0, s, x, pre, query, grad_out, (int)S, D, Q, w, grad_q);
+  hipLaunchKernelGGL(pool_bwd_kernel, dim3((unsigned)B), dim3(256), 0, s, x, pre, query, grad_out, (int)S, D, Q, w, dq_part);
+  MANNER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pool_dq_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, dq_part, B, Q, grad_q);
   MANNER_LAUNCH_CHECK();
   hipLaunchKernelGGL(pool_wdout_kernel, dim3((unsigned)R), dim3(256), 0, s, w, grad_out, R, (int)S, D, add);
   MANNER_LAUNCH_CHECK();
@@ -249,7 +301,11 @@ int manner_hip_embedding_backward(const int64_t* ids, int64_t R, const float* gr
   MANNER_HIP_TRY(hipMemsetAsync(grad_table, 0, (size_t)n_rows * D * sizeof(float), s));
   if (R == 0) return MANNER_HIP_OK;
   if (!ids || !grad_out || R < 0) return fail(MANNER_HIP_E_INVALID, "embedding_backward: bad argument");
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)R), dim3(256), 0, s, ids, grad_out, n_rows, D, padding_idx, grad_table);
+  if (R <= EMBEDDING_ORDERED_MAX)
+    hipLaunchKernelGGL(embedding_bwd_ordered_kernel, dim3((unsigned)R), dim3(256), 0, s, ids, grad_out, (int)R, n_rows, D, padding_idx,
+                       grad_table);
+  else
+    hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)R), dim3(256), 0, s, ids, grad_out, n_rows, D, padding_idx, grad_table);
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }

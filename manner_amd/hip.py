@@ -1860,6 +1860,41 @@ def rows_max_len(store_len: Tensor, rows: Tensor, store_cnt: Optional[Tensor] = 
     return out
 
 
+# ---------------------------------------------------------------- A-Module batches: M-per-class sampling on the device
+def sample_m_per_class(class_off: Tensor, class_members: Tensor, class_label: Tensor, rows: Tensor, store_len: Tensor,
+                       store_cnt: Optional[Tensor], m: int, k: int, nb: int, seed: int, epoch: int):
+    """A whole epoch of M-per-class batches in one call (include/manner_hip.h, "A-Module batches"): ``nb`` batches of ``k`` classes
+    times ``m`` members over the class tables ``class_off`` int64 [L + 1] / ``class_members`` int32 [N] / ``class_label`` int64 [L];
+    ``rows`` int32 [N] maps a data-set index to its store row.  A pure function of (seed, epoch) and the tables.
+    -> (idx int32 [nb * k * m], store rows int32 [nb * k * m], labels int64 [nb * k * m], widths int32 [nb, 2]: per batch the longest
+    token row and entity list, 0 for ``store_cnt`` None).  Nothing is read back; a bad ``rows`` entry raises through the device status
+    word (``check_status``), sizes outside the kernel's bounds raise here, before any launch."""
+    class_off = _dev(class_off, torch.int64, "class_off").contiguous()
+    class_members = _dev(class_members, torch.int32, "class_members").contiguous()
+    class_label = _dev(class_label, torch.int64, "class_label").contiguous()
+    rows = _dev(rows, torch.int32, "rows").contiguous()
+    store_len = _dev(store_len, torch.int32, "store_len").contiguous()
+    if store_cnt is not None:
+        store_cnt = _dev(store_cnt, torch.int32, "store_cnt").contiguous()
+    n_cls, n = class_label.numel(), class_members.numel()
+    if class_off.numel() != n_cls + 1 or rows.numel() != n or (store_cnt is not None and store_cnt.numel() != store_len.numel()):
+        raise ValueError("sample_m_per_class: class_off / rows / store_cnt do not fit class_label, class_members and store_len")
+    dev = rows.device
+    total = max(int(nb), 0) * max(int(k), 0) * max(int(m), 0)
+    if total >= 2 ** 31:
+        raise ValueError("sample_m_per_class: nb * k * m overflows 2^31")
+    idx = torch.empty((total,), dtype=torch.int32, device=dev)
+    out_rows = torch.empty((total,), dtype=torch.int32, device=dev)
+    labels = torch.empty((total,), dtype=torch.int64, device=dev)
+    width = torch.empty((max(int(nb), 0), 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().manner_hip_sample_m_per_class(
+            _ptr(class_off), _ptr(class_members), _ptr(class_label), n_cls, n, _ptr(rows), _ptr(store_len), _ptr(store_cnt),
+            store_len.numel(), m, k, nb, seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), _ptr(idx), _ptr(out_rows), _ptr(labels),
+            _ptr(width), _ptr(device_status(dev).word), _stream()))
+    return idx, out_rows, labels, width
+
+
 def eval_loss(scores: Tensor, labels: Tensor, cand_off: Tensor, supcon: bool = True, temperature: float = 0.1,
               c_max: Optional[int] = None, reduce: bool = True):
     """Loss of ``CRModule.model_step`` (cr_module.py:140-171) from the ragged scores: SupCon on the score matrix
