@@ -11,8 +11,9 @@
 // shared history products and an f32 MFMA linear.  manner_hip_caum_train_all_forward / _backward (after it) are the same loop in train():
 // all columns as B C S rows of one call, column c under its own dropout seed, forward and backward, every product on the matrix cores
 // (wlin_kernel; mwgrad_kernel for the weight gradients, exported alone as manner_hip_wgrad_rows_f32).
-// The per-column workload is small (B = 8, S = 50, widths 400) and latency-bound: plain f32 VALU kernels.  Every reduction across rows runs in a
-// fixed order (no floating-point atomics): two runs give the same bits.
+// The per-column workload is small (B = 8, S = 50, widths 400) and latency-bound: plain f32 VALU kernels — its nn.Linear, forward and
+// all three gradients, is the row kernels of rows_f32.hip (launch_lin_rows, launch_dx_rows, launch_wgrad_rows, launch_colsum_rows).  Every
+// reduction across rows runs in a fixed order (no floating-point atomics): two runs give the same bits.
 #include <math.h>
 
 #include <algorithm>
@@ -25,14 +26,10 @@ namespace {
 constexpr int CA_MAX_S = 256, CA_MAX_W = 1024, CA_MAX_DH = 64;
 constexpr int CA_BLOCK = 256, CA_WAVE = 64, CA_WAVES = CA_BLOCK / CA_WAVE;      // threads per workgroup, lanes per wave, waves per workgroup
 constexpr int CA_FLAT_GRID = 8192;   // most workgroups of a grid-stride elementwise launch
-constexpr int CA_ROWS = 8;       // rows per workgroup of the linear, data-gradient, score and row kernels
-constexpr int CA_OT = 64;        // output features per workgroup of the linear kernel
-constexpr int CA_KS = 128;       // input features per step of the linear kernel (x rows 4 KiB, weight tile CA_OT x (CA_KS + 1) floats = 32 KiB)
-constexpr int CA_OC = 1024;      // output features staged per pass of the data-gradient kernel (32 KiB)
+constexpr int CA_ROWS = 8;       // rows per workgroup of the score and row kernels
 constexpr int CA_LDS = 7168;     // floats of each of the two staged attention operands (2 x 28 KiB)
 constexpr int CA_KT = 64;        // rows of the other side per tile when a (slot, head) pair does not fit CA_LDS or B > 256
 static_assert(CA_KT * CA_MAX_DH <= CA_LDS, "a tile of the largest head fits");
-static_assert(CA_OT * CA_WAVES == CA_BLOCK && CA_WAVES == 4 && CA_KS % CA_WAVES == 0, "lin_kernel: thread = (output feature, K quarter)");
 static_assert(CA_MAX_S % CA_WAVE == 0, "one wave holds a user's scores, CA_MAX_S / CA_WAVE per lane");
 static_assert(CA_KT <= CA_BLOCK, "the statistics of a tile fit one entry per thread");
 static_assert(CA_WAVE == 64, "common.h's wsum / wmax reduce 64 lanes");
@@ -56,119 +53,6 @@ __global__ __launch_bounds__(CA_BLOCK) void pack_kernel(const float* __restrict_
     p2[d] = cv; p2[D + d] = vm;
     if (s == 0) cd[(size_t)b * D + d] = cv;
   }
-}
-
-// ---------------------------------------------------------------- nn.Linear with leading dimensions
-// y[r, o] = act(b[o] + rowadd[r / S, o] + sum_k x[r, k] W[o, k]); x [R, K] contiguous, W rows ldw apart, y rows ldy apart (a column
-// range of a wider buffer).  grid (ceil(R / CA_ROWS), ceil(O / CA_OT)): a workgroup owns CA_ROWS rows x CA_OT output features and walks K
-// in steps of CA_KS, the x rows and the weight tile staged in LDS by whole coalesced rows (the tile padded by one float against bank
-// conflicts); thread = (output feature, wave): each wave takes a quarter of every step on its own chain, and the four partial sums
-// meet in LDS and are added pairwise, in a fixed order.
-// TANH with `deriv` [R, O]: also tanh' = 4 e / (1 + e)^2, e = exp(-2 |pre|), taken from the pre-activation while it is in a register.
-// 1 - y^2 from the rounded y loses 2 y^2 / (1 - y^2) of y's relative error — 18 x at y = 0.95 — and the bias gradients of the dense
-// attention sum hundreds of such terms that cancel.
-template <bool TANH>
-__global__ __launch_bounds__(CA_BLOCK) void lin_kernel(const float* __restrict__ x, const float* __restrict__ W, int ldw, const float* __restrict__ b,
-                                                  const float* __restrict__ rowadd, int S, int64_t R, int K, int O, float* __restrict__ y, int ldy,
-                                                  float* __restrict__ deriv) {
-  __shared__ float xs[CA_ROWS][CA_KS];
-  __shared__ float ws[CA_OT][CA_KS + 1];
-  __shared__ float red[CA_WAVES][CA_ROWS][CA_OT];
-  const int64_t r0 = (int64_t)blockIdx.x * CA_ROWS;
-  const int nr = (int)min((int64_t)CA_ROWS, R - r0);
-  const int o0 = blockIdx.y * CA_OT, oc = threadIdx.x % CA_OT, kq = threadIdx.x / CA_OT;
-  float acc[CA_ROWS];
-#pragma unroll
-  for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = 0.f;
-  for (int k0 = 0; k0 < K; k0 += CA_KS) {
-    const int kc = min(CA_KS, K - k0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < CA_ROWS * CA_KS; i += CA_BLOCK) {
-      const int rr = i / CA_KS, k = i - rr * CA_KS;
-      xs[rr][k] = (rr < nr && k < kc) ? x[(size_t)(r0 + rr) * K + k0 + k] : 0.f;
-    }
-    for (int i = threadIdx.x; i < CA_OT * CA_KS; i += CA_BLOCK) {
-      const int oo = i / CA_KS, k = i - oo * CA_KS;
-      ws[oo][k] = (o0 + oo < O && k < kc) ? W[(size_t)(o0 + oo) * ldw + k0 + k] : 0.f;      // past O or K: zeros, no branch below
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = kq * (CA_KS / CA_WAVES); k < (kq + 1) * (CA_KS / CA_WAVES); ++k) {
-      const float wv = ws[oc][k];
-#pragma unroll
-      for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = fmaf(xs[rr][k], wv, acc[rr]);
-    }
-  }
-#pragma unroll
-  for (int rr = 0; rr < CA_ROWS; ++rr) red[kq][rr][oc] = acc[rr];
-  __syncthreads();
-  const int o = o0 + oc;
-  if (kq == 0 && o < O) {
-    const float bv = b ? b[o] : 0.f;
-#pragma unroll
-    for (int rr = 0; rr < CA_ROWS; ++rr)
-      if (rr < nr) {
-        float v = ((red[0][rr][oc] + red[1][rr][oc]) + (red[2][rr][oc] + red[3][rr][oc])) + bv;
-        if (rowadd) v += rowadd[(size_t)((r0 + rr) / S) * O + o];
-        y[(size_t)(r0 + rr) * ldy + o] = TANH ? tanhf(v) : v;
-        if (TANH && deriv) {
-          const float e = expf(-2.0f * fabsf(v)), den = 1.0f + e;
-          deriv[(size_t)(r0 + rr) * O + o] = 4.0f * e / (den * den);
-        }
-      }
-  }
-}
-// dx[r, k] = (add[r, k] + sum_o dy[r, o] W[o, k]) * mul[r, k]: dy rows ldy apart, W rows ldw apart, dx / add / mul [R, K]
-// contiguous (add, mul may be NULL); `add` may be dx itself (each element is read and written by one thread).
-// grid (ceil(R / CA_ROWS), ceil(K / CA_BLOCK)): thread = input feature (the weight rows are read coalesced), o ascending on one chain.
-__global__ __launch_bounds__(CA_BLOCK) void lin_dx_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ W, int ldw, int64_t R, int K,
-                                                     int O, const float* add, const float* __restrict__ mul, float* dx) {
-  __shared__ float ds[CA_ROWS][CA_OC];
-  const int64_t r0 = (int64_t)blockIdx.x * CA_ROWS;
-  const int nr = (int)min((int64_t)CA_ROWS, R - r0);
-  const int k = blockIdx.y * CA_BLOCK + threadIdx.x;
-  float acc[CA_ROWS];
-#pragma unroll
-  for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = 0.f;
-  for (int o0 = 0; o0 < O; o0 += CA_OC) {
-    const int no = min(CA_OC, O - o0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < CA_ROWS * no; i += CA_BLOCK) {
-      const int rr = i / no, o = i - rr * no;
-      ds[rr][o] = rr < nr ? dy[(size_t)(r0 + rr) * ldy + o0 + o] : 0.f;
-    }
-    __syncthreads();
-    if (k < K)
-      for (int o = 0; o < no; ++o) {
-        const float w = W[(size_t)(o0 + o) * ldw + k];
-#pragma unroll
-        for (int rr = 0; rr < CA_ROWS; ++rr) acc[rr] = fmaf(ds[rr][o], w, acc[rr]);
-      }
-  }
-  if (k < K) {
-#pragma unroll
-    for (int rr = 0; rr < CA_ROWS; ++rr)
-      if (rr < nr) {
-        const size_t at = (size_t)(r0 + rr) * K + k;
-        float v = acc[rr] + (add ? add[at] : 0.f);
-        if (mul) v *= mul[at];
-        dx[at] = v;
-      }
-  }
-}
-
-int launch_lin(bool tanh_act, const float* x, const float* W, int ldw, const float* b, const float* rowadd, int S, int64_t R, int K, int O, float* y,
-               int ldy, hipStream_t s, float* deriv = nullptr) {
-  const dim3 g((unsigned)((R + CA_ROWS - 1) / CA_ROWS), (unsigned)((O + CA_OT - 1) / CA_OT));
-  if (tanh_act) hipLaunchKernelGGL(lin_kernel<true>, g, dim3(CA_BLOCK), 0, s, x, W, ldw, b, rowadd, S, R, K, O, y, ldy, deriv);
-  else hipLaunchKernelGGL(lin_kernel<false>, g, dim3(CA_BLOCK), 0, s, x, W, ldw, b, rowadd, S, R, K, O, y, ldy, deriv);
-  MANNER_LAUNCH_CHECK();
-  return MANNER_HIP_OK;
-}
-int launch_dx(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, const float* add, const float* mul, float* dx, hipStream_t s) {
-  hipLaunchKernelGGL(lin_dx_kernel, dim3((unsigned)((R + CA_ROWS - 1) / CA_ROWS), (unsigned)((K + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, dy, ldy, W, ldw, R, K, O, add, mul, dx);
-  MANNER_LAUNCH_CHECK();
-  return MANNER_HIP_OK;
 }
 
 // ---------------------------------------------------------------- axis-0 attention at any head dim (the fixed-dim family: axis0.hip)
@@ -390,33 +274,34 @@ int a0any_check(const char* who, int64_t L0, int64_t B1, int E, int heads) {
     else CALL(64);                       \
   } while (0)
 
-int launch_a0any_fwd(const float* qkv, float* out, float* stats, int64_t N, int64_t E, int D, int heads, hipStream_t s) {
+// what every launch of the family starts from: the head dim, the plan and the grid (pair tiles, row tiles) over E slots
+struct A0Launch { int dh; A0Plan pl; dim3 g; };
+A0Launch a0_launch(int64_t N, int64_t E, int D, int heads) {
   const int dh = D / heads;
   const A0Plan pl = a0_plan(N, dh);
-  const dim3 g((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
-#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_fwd_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qkv, out, stats, N, (int)E, D, heads, dh, pl)
-  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+  return A0Launch{dh, pl, dim3((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ))};
+}
+int launch_a0any_fwd(const float* qkv, float* out, float* stats, int64_t N, int64_t E, int D, int heads, hipStream_t s) {
+  const A0Launch l = a0_launch(N, E, D, heads);
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_fwd_kernel<DHP_>), l.g, dim3(CA_BLOCK), 0, s, qkv, out, stats, N, (int)E, D, heads, l.dh, l.pl)
+  MANNER_A0ANY_DISPATCH(l.dh, MANNER_A0);
 #undef MANNER_A0
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }
 int launch_a0any_bwd_q(const float* qkv, const float* att, const float* datt, float* dqkv, float* stats, int64_t N, int64_t E, int D, int heads,
                        hipStream_t s) {
-  const int dh = D / heads;
-  const A0Plan pl = a0_plan(N, dh);
-  const dim3 g((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
-#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_bwd_q_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qkv, att, datt, dqkv, stats, N, (int)E, D, heads, dh, pl)
-  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+  const A0Launch l = a0_launch(N, E, D, heads);
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_bwd_q_kernel<DHP_>), l.g, dim3(CA_BLOCK), 0, s, qkv, att, datt, dqkv, stats, N, (int)E, D, heads, l.dh, l.pl)
+  MANNER_A0ANY_DISPATCH(l.dh, MANNER_A0);
 #undef MANNER_A0
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
 }
 int launch_a0any_bwd_kv(const float* qkv, const float* datt, const float* stats, float* dqkv, int64_t N, int64_t E, int D, int heads, hipStream_t s) {
-  const int dh = D / heads;
-  const A0Plan pl = a0_plan(N, dh);
-  const dim3 g((unsigned)((E * heads + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
-#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_bwd_kv_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qkv, datt, stats, dqkv, N, (int)E, D, heads, dh, pl)
-  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+  const A0Launch l = a0_launch(N, E, D, heads);
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0any_bwd_kv_kernel<DHP_>), l.g, dim3(CA_BLOCK), 0, s, qkv, datt, stats, dqkv, N, (int)E, D, heads, l.dh, l.pl)
+  MANNER_A0ANY_DISPATCH(l.dh, MANNER_A0);
 #undef MANNER_A0
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
@@ -678,10 +563,10 @@ __global__ __launch_bounds__(CA_BLOCK) void wlin_kernel(const float* __restrict_
       if (add_bs) v += add_bs[((size_t)b * m.S + s) * O + o];
       if (add_bc) v += add_bc[((size_t)b * m.C + m.c0 + cl) * O + o];
     }
-    if (add_el) v += add_el[(size_t)r * O + o];          // the data gradients: (add + sum) * mul, as lin_dx_kernel
+    if (add_el) v += add_el[(size_t)r * O + o];          // the data gradients: (add + sum) * mul, as dx_rows_kernel
     if (mul_el) v *= mul_el[(size_t)r * O + o];
     y[(size_t)r * ldy + o] = TANH ? tanhf(v) : v;
-    if (TANH && deriv) {                                 // tanh' from the pre-activation, as lin_kernel
+    if (TANH && deriv) {                                 // tanh' from the pre-activation, as lin_rows_kernel
       const float e = expf(-2.0f * fabsf(v)), den = 1.0f + e;
       deriv[(size_t)r * O + o] = 4.0f * e / (den * den);
     }
@@ -744,7 +629,9 @@ int launch_wlin(bool tanh_act, const float* x, int ldx, const float* W, int ldw,
 }
 
 // a0any_fwd_kernel with q, k, v of the pair (e = cl S + s, head) formed on the way into registers and LDS: row n is
-// QH[n, s] + QC[n, c0 + cl] (qh [N, S, 3D], qc [N, C, 3D]); out [(n cp + cl) S + s, D].  The [N, C, S, 3D] tensor is never written.
+// QH[n, s] + QC[n, c0 + cl] (qh [N, S, 3D], qc [N, C, 3D]); out [(n cp + cl) S + s, D], no statistics.  The [N, C, S, 3D] tensor is never
+// written.  A copy of a0any_fwd_kernel's walk, not an instantiation of it: as one body over an operand policy the all-columns forward
+// measured 1.5 - 1.9 % slower than with this copy, twice (profiles/side_kernels/ab_parent_linear.json).
 template <int DHP>
 __global__ __launch_bounds__(CA_BLOCK) void a0sum_fwd_kernel(const float* __restrict__ qh, const float* __restrict__ qc, float* __restrict__ out, int64_t N,
                                                         RowMap m, int D, int heads, int dh, A0Plan pl) {
@@ -802,12 +689,9 @@ __global__ __launch_bounds__(CA_BLOCK) void a0sum_fwd_kernel(const float* __rest
   }
 }
 int launch_a0sum_fwd(const float* qh, const float* qc, float* out, int64_t N, RowMap m, int D, int heads, hipStream_t s) {
-  const int dh = D / heads;
-  const A0Plan pl = a0_plan(N, dh);
-  const int64_t pairs = (int64_t)m.cp * m.S * heads;
-  const dim3 g((unsigned)((pairs + pl.P - 1) / pl.P), (unsigned)((N + pl.RQ - 1) / pl.RQ));
-#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0sum_fwd_kernel<DHP_>), g, dim3(CA_BLOCK), 0, s, qh, qc, out, N, m, D, heads, dh, pl)
-  MANNER_A0ANY_DISPATCH(dh, MANNER_A0);
+  const A0Launch l = a0_launch(N, (int64_t)m.cp * m.S, D, heads);
+#define MANNER_A0(DHP_) hipLaunchKernelGGL((a0sum_fwd_kernel<DHP_>), l.g, dim3(CA_BLOCK), 0, s, qh, qc, out, N, m, D, heads, l.dh, l.pl)
+  MANNER_A0ANY_DISPATCH(l.dh, MANNER_A0);
 #undef MANNER_A0
   MANNER_LAUNCH_CHECK();
   return MANNER_HIP_OK;
@@ -1156,10 +1040,10 @@ int manner_hip_relu_backward(const float* x, const float* grad_out, float* grad_
 
 int manner_hip_linear_tanh(const float* x, const float* weight, const float* bias, int64_t R, int32_t K, int32_t O, float* y,
                            manner_hip_stream_t stream) {
-  if (R < 0 || K <= 0 || O <= 0 || R > 0x7fffffffll || O > 65535 * CA_OT) return fail(MANNER_HIP_E_INVALID, "linear_tanh: bad shape");
+  if (R < 0 || K <= 0 || O <= 0 || R > 0x7fffffffll || O > 65535 * LIN_ROWS_OT) return fail(MANNER_HIP_E_INVALID, "linear_tanh: bad shape");
   if (R == 0) return MANNER_HIP_OK;
   if (!x || !weight || !y) return fail(MANNER_HIP_E_INVALID, "linear_tanh: null pointer");
-  return launch_lin(true, x, weight, K, bias, nullptr, 1, R, K, O, y, O, (hipStream_t)stream);
+  return launch_lin_rows(true, x, weight, K, bias, nullptr, 1, R, K, O, y, O, nullptr, (hipStream_t)stream);
 }
 
 int manner_hip_tanh_backward(const float* y, const float* grad_out, float* grad_pre, int64_t n, manner_hip_stream_t stream) {
@@ -1229,20 +1113,20 @@ int manner_hip_caum_user_forward(const float* x, const float* c, int64_t c_strid
   hipLaunchKernelGGL(pack_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, x, c, c_stride, Si, D, d1, d2, sv.a1, sv.a2, sv.cd);
   MANNER_LAUNCH_CHECK();
   // candi-cnn into cat[:, :F]; candi-selfatt: Linear, in-projection, attention along B, out-projection into cat[:, F:]
-  if ((rc = launch_lin(false, sv.a1, params[P_W1], 4 * D, params[P_B1], nullptr, 1, R, 4 * D, F, sv.cat, FU, s))) return rc;
-  if ((rc = launch_lin(false, sv.a2, params[P_W2], 2 * D, params[P_B2], nullptr, 1, R, 2 * D, U, sv.h2, U, s))) return rc;
-  if ((rc = launch_lin(false, sv.h2, params[P_WIN], U, params[P_BIN], nullptr, 1, R, U, 3 * U, sv.qkv, 3 * U, s))) return rc;
+  if ((rc = launch_lin_rows(false, sv.a1, params[P_W1], 4 * D, params[P_B1], nullptr, 1, R, 4 * D, F, sv.cat, FU, nullptr, s))) return rc;
+  if ((rc = launch_lin_rows(false, sv.a2, params[P_W2], 2 * D, params[P_B2], nullptr, 1, R, 2 * D, U, sv.h2, U, nullptr, s))) return rc;
+  if ((rc = launch_lin_rows(false, sv.h2, params[P_WIN], U, params[P_BIN], nullptr, 1, R, U, 3 * U, sv.qkv, 3 * U, nullptr, s))) return rc;
   if ((rc = launch_a0any_fwd(sv.qkv, sv.att, sv.stats, B, S, U, heads, s))) return rc;
-  if ((rc = launch_lin(false, sv.att, params[P_WOUT], U, params[P_BOUT], nullptr, 1, R, U, U, sv.cat + F, FU, s))) return rc;
+  if ((rc = launch_lin_rows(false, sv.att, params[P_WOUT], U, params[P_BOUT], nullptr, 1, R, U, U, sv.cat + F, FU, nullptr, s))) return rc;
   if (p > 0.f) {
     hipLaunchKernelGGL(drop_inplace_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, sv.cat, R * FU, d3);
     MANNER_LAUNCH_CHECK();
   }
-  if ((rc = launch_lin(false, sv.cat, params[P_W3], FU, params[P_B3], nullptr, 1, R, FU, U, sv.all, U, s))) return rc;
+  if ((rc = launch_lin_rows(false, sv.cat, params[P_W3], FU, params[P_B3], nullptr, 1, R, FU, U, sv.all, U, nullptr, s))) return rc;
   // candi-att: the candidate half of dense_att.linear once per user, then the two tanh layers over the rows
-  if ((rc = launch_lin(false, sv.cd, params[P_WA] + U, 2 * U, params[P_BA], nullptr, 1, B, D, H1, sv.ct, H1, s))) return rc;
-  if ((rc = launch_lin(true, sv.all, params[P_WA], 2 * U, nullptr, sv.ct, Si, R, U, H1, sv.t1, H1, s, sv.d1))) return rc;
-  if ((rc = launch_lin(true, sv.t1, params[P_WB], H1, params[P_BB], nullptr, 1, R, H1, H2, sv.t2, H2, s, sv.d2))) return rc;
+  if ((rc = launch_lin_rows(false, sv.cd, params[P_WA] + U, 2 * U, params[P_BA], nullptr, 1, B, D, H1, sv.ct, H1, nullptr, s))) return rc;
+  if ((rc = launch_lin_rows(true, sv.all, params[P_WA], 2 * U, nullptr, sv.ct, Si, R, U, H1, sv.t1, H1, sv.d1, s))) return rc;
+  if ((rc = launch_lin_rows(true, sv.t1, params[P_WB], H1, params[P_BB], nullptr, 1, R, H1, H2, sv.t2, H2, sv.d2, s))) return rc;
   hipLaunchKernelGGL(score_kernel, dim3((unsigned)((R + CA_ROWS - 1) / CA_ROWS)), dim3(CA_BLOCK), 0, s, sv.t2, params[P_WC], params[P_BC], sv.all, sv.cd, R,
                      Si, H2, U, sv.score, sv.g);
   MANNER_LAUNCH_CHECK();
@@ -1304,11 +1188,11 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
   // dense_att.linear2
   if ((rc = launch_wgrad_rows(w.dt2, H2, sv.t1, R, H1, H2, w.part, grads[P_WB], H1, s))) return rc;
   if ((rc = launch_colsum_rows(w.dt2, H2, R, H2, grads[P_BB], s))) return rc;
-  if ((rc = launch_dx(w.dt2, H2, params[P_WB], H1, R, H1, H2, nullptr, sv.d1, w.dt1, s))) return rc;
+  if ((rc = launch_dx_rows(w.dt2, H2, params[P_WB], H1, R, H1, H2, nullptr, sv.d1, w.dt1, s))) return rc;
   // dense_att.linear: the history half over the rows, the candidate half over the users (d ct[b] = sum_s d t1[b, s])
   if ((rc = launch_wgrad_rows(w.dt1, H1, sv.all, R, U, H1, w.part, grads[P_WA], 2 * U, s))) return rc;
   if ((rc = launch_colsum_rows(w.dt1, H1, R, H1, grads[P_BA], s))) return rc;
-  if ((rc = launch_dx(w.dt1, H1, params[P_WA], 2 * U, R, U, H1, w.dall, nullptr, w.dall, s))) return rc;
+  if ((rc = launch_dx_rows(w.dt1, H1, params[P_WA], 2 * U, R, U, H1, w.dall, nullptr, w.dall, s))) return rc;
   hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((H1 + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, (const float*)nullptr, w.dt1, H1, 0,
                      (const float*)nullptr, 0, (const float*)nullptr, Si, H1, d1, false, w.dct);
   MANNER_LAUNCH_CHECK();
@@ -1317,11 +1201,11 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
   hipLaunchKernelGGL(segsum_kernel, dim3((unsigned)B, (unsigned)((U + CA_BLOCK - 1) / CA_BLOCK)), dim3(CA_BLOCK), 0, s, w.wq, sv.all, U, 0, (const float*)nullptr, 0,
                      (const float*)nullptr, Si, U, d1, false, w.dcd);
   MANNER_LAUNCH_CHECK();
-  if ((rc = launch_dx(w.dct, H1, params[P_WA] + U, 2 * U, B, D, H1, w.dcd, nullptr, w.dcd, s))) return rc;
+  if ((rc = launch_dx_rows(w.dct, H1, params[P_WA] + U, 2 * U, B, D, H1, w.dcd, nullptr, w.dcd, s))) return rc;
   // linear3 and dropout3
   if ((rc = launch_wgrad_rows(w.dall, U, sv.cat, R, FU, U, w.part, grads[P_W3], FU, s))) return rc;
   if ((rc = launch_colsum_rows(w.dall, U, R, U, grads[P_B3], s))) return rc;
-  if ((rc = launch_dx(w.dall, U, params[P_W3], FU, R, FU, U, nullptr, nullptr, w.dcat, s))) return rc;
+  if ((rc = launch_dx_rows(w.dall, U, params[P_W3], FU, R, FU, U, nullptr, nullptr, w.dcat, s))) return rc;
   if (p > 0.f) {
     hipLaunchKernelGGL(drop_inplace_kernel, dim3(flat_grid(R * FU)), dim3(CA_BLOCK), 0, s, w.dcat, R * FU, d3);
     MANNER_LAUNCH_CHECK();
@@ -1329,21 +1213,21 @@ int manner_hip_caum_user_backward(const float* const* params, const float* grad_
   // candi-selfatt: out-projection, attention, in-projection, linear2
   if ((rc = launch_wgrad_rows(w.dcat + F, FU, sv.att, R, U, U, w.part, grads[P_WOUT], U, s))) return rc;
   if ((rc = launch_colsum_rows(w.dcat + F, FU, R, U, grads[P_BOUT], s))) return rc;
-  if ((rc = launch_dx(w.dcat + F, FU, params[P_WOUT], U, R, U, U, nullptr, nullptr, w.datt, s))) return rc;
+  if ((rc = launch_dx_rows(w.dcat + F, FU, params[P_WOUT], U, R, U, U, nullptr, nullptr, w.datt, s))) return rc;
   if ((rc = launch_a0any_bwd_q(sv.qkv, sv.att, w.datt, w.dqkv, sv.stats, B, S, U, heads, s))) return rc;
   if ((rc = launch_a0any_bwd_kv(sv.qkv, w.datt, sv.stats, w.dqkv, B, S, U, heads, s))) return rc;
   if ((rc = launch_wgrad_rows(w.dqkv, 3 * U, sv.h2, R, U, 3 * U, w.part, grads[P_WIN], U, s))) return rc;
   if ((rc = launch_colsum_rows(w.dqkv, 3 * U, R, 3 * U, grads[P_BIN], s))) return rc;
   // the K third of d in_proj_bias is zero in exact arithmetic (a shift of every key moves every logit of a row alike)
   MANNER_HIP_TRY(hipMemsetAsync(grads[P_BIN] + U, 0, (size_t)U * sizeof(float), s));
-  if ((rc = launch_dx(w.dqkv, 3 * U, params[P_WIN], U, R, U, 3 * U, nullptr, nullptr, w.dh2, s))) return rc;
+  if ((rc = launch_dx_rows(w.dqkv, 3 * U, params[P_WIN], U, R, U, 3 * U, nullptr, nullptr, w.dh2, s))) return rc;
   if ((rc = launch_wgrad_rows(w.dh2, U, sv.a2, R, 2 * D, U, w.part, grads[P_W2], 2 * D, s))) return rc;
   if ((rc = launch_colsum_rows(w.dh2, U, R, U, grads[P_B2], s))) return rc;
-  if ((rc = launch_dx(w.dh2, U, params[P_W2], 2 * D, R, 2 * D, U, nullptr, nullptr, w.da2, s))) return rc;
+  if ((rc = launch_dx_rows(w.dh2, U, params[P_W2], 2 * D, R, 2 * D, U, nullptr, nullptr, w.da2, s))) return rc;
   // candi-cnn: linear1 from cat[:, :F]
   if ((rc = launch_wgrad_rows(w.dcat, FU, sv.a1, R, 4 * D, F, w.part, grads[P_W1], 4 * D, s))) return rc;
   if ((rc = launch_colsum_rows(w.dcat, FU, R, F, grads[P_B1], s))) return rc;
-  if ((rc = launch_dx(w.dcat, FU, params[P_W1], 4 * D, R, 4 * D, F, nullptr, nullptr, w.da1, s))) return rc;
+  if ((rc = launch_dx_rows(w.dcat, FU, params[P_W1], 4 * D, R, 4 * D, F, nullptr, nullptr, w.da1, s))) return rc;
   // d x: the three windows and the self-attention operand; d c: the sums over the slots, through dropout1
   hipLaunchKernelGGL(window_dx_kernel, dim3((unsigned)R), dim3(CA_BLOCK), 0, s, w.da1, w.da2, Si, D, d2, grad_x);
   MANNER_LAUNCH_CHECK();

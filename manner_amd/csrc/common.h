@@ -226,10 +226,19 @@ int wlin_f32(bool tanh_act, const float* x, int ldx, const float* W, int ldw, co
 int wlin_dx_f32(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, float* dx, float* wt, hipStream_t stream);
 
 // ------------------------------------------------------------------ f32 row kernels of the side operators (rows_f32.hip)
-// gi [R, O] = b + x_r W^T over the rows r = (b S + t) C + c of x (row at x + b xsb + t xss + c K, zeros where t >= len[b]; C = 1: the
-// plain (b, t) rows); W [O, K]; xs (may be NULL) [R, K] receives the rows as read
+// y [R, O] (rows ldy apart) = act(b + rowadd[r / S] + x W^T): x [R, K] contiguous, W [O, K] rows ldw apart, b [O] and rowadd [R / S, O]
+// may be NULL; act = tanh or none; deriv (tanh only, may be NULL) [R, O] receives tanh' of the pre-activation.  R >= 1,
+// O <= 65535 * LIN_ROWS_OT
+constexpr int LIN_ROWS_OT = 64;      // output features per workgroup
+int launch_lin_rows(bool tanh_act, const float* x, const float* W, int ldw, const float* b, const float* rowadd, int S, int64_t R, int K, int O, float* y,
+                    int ldy, float* deriv, hipStream_t stream);
+// gi [R, O] = b + x_r W^T on the same kernel over the rows r = (b S + t) C + c of x (row at x + b xsb + t xss + c K, zeros where
+// t >= len[b]; C = 1: the plain (b, t) rows); W [O, K]; xs (may be NULL) [R, K] receives the rows as read
 int launch_proj_rows(const float* x, int64_t xsb, int64_t xss, const int64_t* len, const float* W, const float* b, int S, int C, int64_t R, int K, int O,
                      float* gi, float* xs, hipStream_t stream);
+// dx [R, K] = (add + dy W) * mul: dy rows ldy apart, W [O, K] rows ldw apart, add / mul [R, K] may be NULL, add may be dx; R >= 1
+int launch_dx_rows(const float* dy, int ldy, const float* W, int ldw, int64_t R, int K, int O, const float* add, const float* mul, float* dx,
+                   hipStream_t stream);
 // dW [O, K] (rows ldo apart) = sum_r dy[r, o] x[r, k]: dy rows ldy apart, x [R, K] contiguous, R >= 1.  The rows are summed in
 // wgrad_rows_groups(R) groups; part holds wgrad_rows_part_floats(R, K, O) floats (unused, may be NULL, with one group)
 constexpr int WGRAD_MAX_GROUPS = 16, WGRAD_GROUP_ROWS = 64;      // row groups at most, rows per group at least

@@ -1,6 +1,7 @@
 // SURVEY §8f-3, the small operators of the training step: backward passes of nn.Linear and AdditiveAttention
 // (manner/models/components/attention.py:12-29), nn.Embedding with padding_idx, and dropout on a flat tensor; the axis-0 multi-head
-// attention of the entity branch, forward and backward, is axis0.hip.  The tensors are small (entity dim 100, query dim 200, a few
+// attention of the entity branch, forward and backward, is axis0.hip; nn.Linear's data gradient and bias gradient are the shared row
+// kernels of rows_f32.hip (launch_dx_rows, launch_colsum_rows), its weight gradient is here.  The tensors are small (entity dim 100, query dim 200, a few
 // thousand rows): plain f32 VALU kernels, each one the textbook derivative of the forward kernel in entity.hip / scoring.hip.
 // Composed into autograd Functions by manner_amd/train.py.
 #include <math.h>
@@ -18,40 +19,6 @@ __global__ __launch_bounds__(256) void dropout_flat_kernel(const float* x, float
 }
 
 // ---------------------------------------------------------------- nn.Linear backward: y = x W^T + b, x [R, K], W [O, K]
-constexpr int LB_ROWS = 8;
-// dx[r, k] = sum_o dy[r, o] W[o, k]  (+ add[r, k] when `add` != NULL)
-constexpr int LB_OC = 2048;                          // output features staged per pass (8 rows x 2048 floats = 64 KiB of LDS)
-__global__ __launch_bounds__(256) void lin_bwd_x_kernel(const float* __restrict__ dy, const float* __restrict__ W, int64_t R, int K,
-                                                        int O, const float* __restrict__ add, float* __restrict__ dx) {
-  extern __shared__ float ds[];                      // [LB_ROWS][min(O, LB_OC)]
-  const int64_t r0 = (int64_t)blockIdx.x * LB_ROWS;
-  const int nr = (int)min((int64_t)LB_ROWS, R - r0);
-  const int oc = O < LB_OC ? O : LB_OC;
-  // (K <= 256 * 4 per thread pass: the accumulators of one k live across the passes over O)
-  for (int k0 = 0; k0 < K; k0 += 256) {
-    const int k = k0 + threadIdx.x;
-    float acc[LB_ROWS];
-#pragma unroll
-    for (int rr = 0; rr < LB_ROWS; ++rr) acc[rr] = 0.f;
-    for (int o0 = 0; o0 < O; o0 += oc) {
-      const int no = min(oc, O - o0);
-      __syncthreads();
-      for (int i = threadIdx.x; i < nr * no; i += 256) { const int rr = i / no, o = i - rr * no; ds[rr * oc + o] = dy[(r0 + rr) * O + o0 + o]; }
-      __syncthreads();
-      if (k < K)
-        for (int o = 0; o < no; ++o) {
-          const float w = W[(size_t)(o0 + o) * K + k];
-#pragma unroll
-          for (int rr = 0; rr < LB_ROWS; ++rr) acc[rr] = fmaf(ds[rr * oc + o], w, acc[rr]);
-        }
-    }
-    if (k < K) {
-#pragma unroll
-      for (int rr = 0; rr < LB_ROWS; ++rr)
-        if (rr < nr) dx[(r0 + rr) * K + k] = acc[rr] + (add ? add[(r0 + rr) * K + k] : 0.f);
-    }
-  }
-}
 // dW[o, k] = sum_r dy[r, o] x[r, k]: grid (ceil(K / 256), O); rows gathered through `gather` when x is an embedding table
 __global__ __launch_bounds__(256) void lin_bwd_w_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t R, int K,
                                                         int O, float* __restrict__ dW) {
@@ -235,11 +202,8 @@ int manner_hip_linear_backward(const float* x, const float* weight, const float*
     return MANNER_HIP_OK;
   }
   if (!grad_y || (grad_x && !weight) || (grad_w && !x)) return fail(MANNER_HIP_E_INVALID, "linear_backward: null pointer");
-  if (grad_x) {
-    hipLaunchKernelGGL(lin_bwd_x_kernel, dim3((unsigned)((R + LB_ROWS - 1) / LB_ROWS)), dim3(256), LB_ROWS * (O < LB_OC ? O : LB_OC) * sizeof(float), s, grad_y,
-                       weight, R, K, O, add_to_dx, grad_x);
-    MANNER_LAUNCH_CHECK();
-  }
+  int rc;
+  if (grad_x && (rc = launch_dx_rows(grad_y, O, weight, K, R, K, O, add_to_dx, nullptr, grad_x, s))) return rc;
   if (grad_w) {
     hipLaunchKernelGGL(lin_bwd_w_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)O), dim3(256), 0, s, grad_y, x, R, K, O, grad_w);
     MANNER_LAUNCH_CHECK();

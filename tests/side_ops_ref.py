@@ -330,7 +330,9 @@ def linear_terms(x, weight, bias, dy, absolute=False, dtype=np.float64):
     return out
 
 
-LINEAR_SHAPES = ((1, 4, 1), (9, 8, 2049), (9, 8, 4100), (17, 257, 300), (8, 512, 5), (7, 2049, 3), (9, 4096, 5), (65, 8, 70))
+# (9, 300, 1030): the data gradient's second tile of 256 input features (44 of them) and its second pass of 1024 staged output features
+# (6 of them) in one launch, with a second row tile of one row
+LINEAR_SHAPES = ((1, 4, 1), (9, 8, 2049), (9, 8, 4100), (17, 257, 300), (8, 512, 5), (7, 2049, 3), (9, 4096, 5), (65, 8, 70), (9, 300, 1030))
 
 
 @functools.lru_cache(maxsize=None)
