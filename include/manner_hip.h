@@ -1052,6 +1052,45 @@ int manner_hip_seqcls_head(const float* x, int64_t ldx, const float* dense_w, co
                            int64_t N, int32_t H, int32_t L, int32_t pos_idx, int32_t neg_idx, float* probs, int32_t* label, float* score,
                            manner_hip_stream_t stream);
 
+/* ---- t-SNE of the A-Module's embedding plots (csrc/tsne.hip; f32, f64 only in final fixed-order sums; additive exports) ---------------
+ * The reference's AModule.on_validation_epoch_end / on_test_epoch_end (manner/models/a_module.py:150-173, 191-212) call
+ * MulticoreTSNE(n_jobs=8).fit_transform on the CPU.  These five entries are the arithmetic of manner_amd.manifold.TSNE, the published
+ * method (kNN affinities at 3 x perplexity neighbours, gains, momentum, early exaggeration) with EXACT repulsive forces: the Barnes-Hut
+ * `angle` has no meaning here.  No floating-point atomic, no grid-wide barrier or counter; every grid comes from the shape alone: two
+ * runs give the same bits.  Bounds of all five: 1 <= k <= 255, 0 <= N <= 2^20, N - 1 >= k (but for tsne_affinities, whose rows are searched
+ * one by one, and tsne_repulsion, which has no k); N == 0 launches nothing and returns OK.  A bad
+ * shape or a null pointer is MANNER_HIP_E_INVALID with a message that names the entry, before any launch.
+ *
+ * manner_hip_knn_rows_f32: x [N, D] (1 <= D <= 1024) -> idx int32 [N, k], d2 [N, k]: the k nearest OTHER rows of every row by squared
+ *   Euclidean distance, ascending by (d2, idx) — equal distances resolve to the lower row index.  The search is exact; a distance is one
+ *   fmaf chain of squared differences over the features in ascending order (not the Gram form).  A row whose distances are NaN leaves
+ *   idx -1 in the places it could not fill.
+ * manner_hip_tsne_affinities: d2 [N, k] -> p [N, k], beta [N].  Per row the binary search for the beta at which p_j ~ exp(-beta d2_j) has
+ *   entropy log(perplexity) within 1e-5: from beta = 1, doubled or halved while the far bound is open, bisected afterwards, at most 200
+ *   trips.  Distances are taken relative to the row's smallest (p and the entropy do not change; nothing underflows to an empty sum), so
+ *   a row of equal or of zero distances is uniform; beta saturates at FLT_MAX.
+ * manner_hip_tsne_repulsion: y [N, 2] -> part [split, N, 4] = per row and j slice (sum q^2 dx, sum q^2 dy, sum q, 0) over ALL j of the
+ *   slice, q = 1 / (1 + |y_i - y_j|^2) by the hardware reciprocal; zpart f64 [split * ceil(N / 512)] = per workgroup the sum of its rows'
+ *   sum q.  The self pair is not branched on: its q is exactly 1 and its force exactly 0, so Z = (sum of zpart) - N.  `split` must be the
+ *   launcher's own function of N (manner_amd.hip.tsne_j_split); a row's partials are added in ascending slice order by the consumer.
+ * manner_hip_tsne_step: one iteration.  dY_i = exaggeration sum_j P_ij q_ij (y_i - y_j) - (1 / Z) sum_j q_ij^2 (y_i - y_j), P gathered
+ *   from the directed edge list out_idx / out_p [N, k] (edge (i -> j, p) adds p / (2 N) to P_ij and to P_ji) and its transpose: the incoming
+ *   edges of row i are in_src / in_p [in_off[i], in_off[i + 1]) (in_off int64 [N + 1], n_in edges in all), any number per row.  Then
+ *   gains = sign(dY) != sign(u) ? gains + 0.2 : gains * 0.8, floored at 0.01 (sign(0) = 0); u = momentum u - learning_rate gains dY;
+ *   y_out = y + u, less its column means (a second launch; ypart f64 [2 ceil(N / 64)] is its scratch).  u, gains [N, 2] in place; y_out
+ *   must not be y.  An edge whose index is outside [0, N) is skipped.
+ * manner_hip_tsne_kl: kl f64 [1] = sum P log(P / Q) over the non-zero entries of the symmetrised P, Q = q / Z, from y, the zpart of a
+ *   repulsion call on the same y, and the outgoing edges; klpart f64 [ceil(N / 64)] is scratch. */
+int manner_hip_knn_rows_f32(const float* x, int64_t N, int32_t D, int32_t k, int32_t* idx, float* d2, manner_hip_stream_t stream);
+int manner_hip_tsne_affinities(const float* d2, int64_t N, int32_t k, float perplexity, float* p, float* beta, manner_hip_stream_t stream);
+int manner_hip_tsne_repulsion(const float* y, int64_t N, int32_t split, float* part, double* zpart, manner_hip_stream_t stream);
+int manner_hip_tsne_step(const float* y, const float* part, const double* zpart, int32_t split, const int32_t* out_idx, const float* out_p,
+                         int32_t k, const int64_t* in_off, const int32_t* in_src, const float* in_p, int64_t n_in, int64_t N,
+                         float exaggeration, float momentum, float learning_rate, float* u, float* gains, float* y_out, double* ypart,
+                         manner_hip_stream_t stream);
+int manner_hip_tsne_kl(const float* y, const double* zpart, int32_t split, const int32_t* out_idx, const float* out_p, int32_t k, int64_t N,
+                       double* klpart, double* kl, manner_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

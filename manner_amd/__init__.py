@@ -4,9 +4,9 @@
 everything else is imported from the submodules (``hip``, ``hotpath``, ``distributed``, ``train``, ``models.components``)."""
 
 
-def install(reference_root=None, baselines=(), annotator=False):
+def install(reference_root=None, baselines=(), annotator=False, tsne=False):
     from .binding import install as _install
-    return _install(reference_root, baselines, annotator=annotator)
+    return _install(reference_root, baselines, annotator=annotator, tsne=tsne)
 
 
 def uninstall():

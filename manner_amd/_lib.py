@@ -198,6 +198,12 @@ SIGNATURES = {
     "manner_hip_adv_loss": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
     "manner_hip_adv_loss_backward": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "manner_hip_seqcls_head": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "manner_hip_knn_rows_f32": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P]),
+    "manner_hip_tsne_affinities": (C.c_int, [_P, _I64, _I32, C.c_float, _P, _P, _P]),
+    "manner_hip_tsne_repulsion": (C.c_int, [_P, _I64, _I32, _P, _P, _P]),
+    "manner_hip_tsne_step": (C.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I64, _I64, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P,
+                                       _P]),
+    "manner_hip_tsne_kl": (C.c_int, [_P, _P, _I32, _P, _P, _I32, _I64, _P, _P, _P]),
 }
 
 _lib = None

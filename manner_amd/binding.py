@@ -84,6 +84,13 @@ modules that hold the name: ``manner.data.components.sentiment_annotator`` and `
 the class by name.  The mirror has no hub access: the frames' ``SentimentAnnotator(name, max_length)`` call then needs ``name`` to be
 a local HF directory.  Nothing else of ``manner.data`` is touched.
 
+``install(tsne=True)`` (a keyword of its own, default off) rebinds the name ``TSNE`` of ``manner.models.a_module`` — the reference's
+``from MulticoreTSNE import MulticoreTSNE as TSNE`` (a_module.py:9), called by ``on_validation_epoch_end`` / ``on_test_epoch_end``
+(a_module.py:150-173, 191-212) — to ``manner_amd.manifold.TSNE`` (csrc/tsne.hip: exact forces, ``angle`` ignored, not the package's bits).
+Where the ``MulticoreTSNE`` package is not importable a shim module of that name, whose ``MulticoreTSNE`` attribute is the mirror, is
+registered in ``sys.modules`` first, so that line 9 imports; ``uninstall()`` restores the name and removes the shim (an ``a_module`` that was
+first imported through the shim never held another class: it keeps the mirror).  A plain ``install()`` touches neither.
+
 Use (no reference source line changes):
 
     python -m manner_amd.run manner/train.py experiment=cr_module_mind_title_scl_lf      # = install() + runpy of the script
@@ -96,7 +103,9 @@ or two lines at the top of ``manner/train.py`` / ``manner/eval.py``:  ``import m
 from __future__ import annotations
 
 import importlib
+import importlib.util
 import sys
+import types
 from typing import Dict, List, Optional, Sequence, Tuple
 
 TARGETS = {
@@ -145,13 +154,53 @@ def _install_annotator(report: Dict[str, List[str]]) -> None:
         report.setdefault(name, []).append("SentimentAnnotator")
 
 
-def install(reference_root: Optional[str] = None, baselines: Sequence[str] = (), annotator: bool = False) -> Dict[str, List[str]]:
+TSNE_MODULE, TSNE_PACKAGE = "manner.models.a_module", "MulticoreTSNE"
+_tsne_shim: Optional[types.ModuleType] = None          # the stand-in registered as sys.modules["MulticoreTSNE"], if this module made one
+
+
+def _install_tsne(report: Dict[str, List[str]]) -> None:
+    global _tsne_shim
+    from .manifold import TSNE as mirror
+    real = None                                          # the package's class, where the package is there
+    pkg = sys.modules.get(TSNE_PACKAGE)
+    if pkg is None:
+        try:
+            found = importlib.util.find_spec(TSNE_PACKAGE) is not None
+        except (ImportError, ValueError):
+            found = False
+        if found:
+            pkg = importlib.import_module(TSNE_PACKAGE)
+        else:
+            pkg = types.ModuleType(TSNE_PACKAGE)
+            pkg.__doc__ = "stand-in registered by manner_amd.install(tsne=True): MulticoreTSNE is manner_amd.manifold.TSNE"
+            pkg.MulticoreTSNE = mirror
+            sys.modules[TSNE_PACKAGE] = pkg
+            _tsne_shim = pkg
+    if pkg is not _tsne_shim:
+        real = getattr(pkg, "MulticoreTSNE", None)
+    mod = importlib.import_module(TSNE_MODULE)
+    for attr, val in list(vars(mod).items()):
+        if val is mirror:
+            if attr == "TSNE" and _tsne_shim is not None and "TSNE" not in _installed.get(TSNE_MODULE, {}):
+                # imported through the shim: the name was never anything else
+                report.setdefault(TSNE_MODULE, []).append(attr)
+            continue
+        if (attr == "TSNE" and isinstance(val, type)) or (real is not None and val is real):
+            _installed.setdefault(TSNE_MODULE, {}).setdefault(attr, val)
+            setattr(mod, attr, mirror)
+            report.setdefault(TSNE_MODULE, []).append(attr)
+
+
+def install(reference_root: Optional[str] = None, baselines: Sequence[str] = (), annotator: bool = False,
+            tsne: bool = False) -> Dict[str, List[str]]:
     """Rebind the mirrored classes inside the reference's ``manner.models.components`` modules.  ``reference_root``: a checkout
     of andreeaiana/manner to put on ``sys.path`` when ``manner`` is not importable yet.  ``baselines``: opt-in sets of further classes
     (``"miner"``: MINERNewsEncoder, PolyAttention, TargetAwareAttention; ``"caum_plm"``: CAUMCategoryEncoder, CAUMNewsEncoder,
     CAUMUserEncoder, DenseAttention; ``"lstur_plm"``: LSTURCategoryEncoder, LSTURNewsEncoder, LSTURUserEncoder; ``"mins_plm"``:
     NAMLCategoryEncoder, NAMLNewsEncoder, MINSUserEncoder; ``"naml_plm"``: NAMLCategoryEncoder, NAMLNewsEncoder); an unknown name raises
-    ValueError.  ``annotator``: also rebind ``SentimentAnnotator`` in the reference's data components (off by default).  Returns {module: [rebound
+    ValueError.  ``annotator``: also rebind ``SentimentAnnotator`` in the reference's data components (off by default).  ``tsne``: also rebind
+    ``manner.models.a_module.TSNE`` to ``manner_amd.manifold.TSNE``, behind a ``MulticoreTSNE`` shim module where that package is missing (off by
+    default).  Returns {module: [rebound
     names]} (also the aliases patched in already-imported ``manner.*`` modules).  Idempotent; ``uninstall()`` restores the originals."""
     targets = _targets(baselines)
     if reference_root and reference_root not in sys.path:
@@ -193,6 +242,8 @@ def install(reference_root: Optional[str] = None, baselines: Sequence[str] = (),
                     report.setdefault(name, []).append(attr)
     if annotator:
         _install_annotator(report)
+    if tsne:
+        _install_tsne(report)
     return report
 
 
@@ -204,7 +255,18 @@ def uninstall() -> None:
             for n, orig in kept.items():
                 setattr(mod, n, orig)
     _installed.clear()
+    global _tsne_shim
+    if _tsne_shim is not None:
+        if sys.modules.get(TSNE_PACKAGE) is _tsne_shim:
+            del sys.modules[TSNE_PACKAGE]
+        _tsne_shim = None
 
 
 def installed() -> Dict[str, List[str]]:
-    return {m: sorted(k) for m, k in _installed.items() if k}
+    out = {m: sorted(k) for m, k in _installed.items() if k}
+    if _tsne_shim is not None:
+        out[TSNE_PACKAGE] = ["MulticoreTSNE"]
+        mod = sys.modules.get(TSNE_MODULE)
+        if mod is not None and getattr(mod, "TSNE", None) is _tsne_shim.MulticoreTSNE and "TSNE" not in _installed.get(TSNE_MODULE, {}):
+            out.setdefault(TSNE_MODULE, []).append("TSNE")
+    return out

@@ -1919,3 +1919,103 @@ def eval_loss(scores: Tensor, labels: Tensor, cand_off: Tensor, supcon: bool = T
         return losses.sum() * 0                       # losses.py:24-25, 40: no positive or no negative pair in the batch
     nz = losses > 0
     return torch.where(nz.any(), (losses * nz).sum() / nz.sum().clamp(min=1), losses.sum() * 0)
+
+
+# ---------------------------------------------------------------- t-SNE (csrc/tsne.hip)
+# the launchers' tiles, for the tests: rows / j rows per workgroup of the repulsion kernel, query / candidate rows per tile of the
+# neighbour search, rows per workgroup of the step and KL kernels
+TSNE_TILE_I, TSNE_TILE_J, KNN_TILE_Q, KNN_TILE_C, TSNE_STEP_ROWS = 512, 512, 32, 64, 64
+_TSNE_TARGET_WG = 1024
+
+
+def tsne_j_split(n: int) -> int:
+    """The number of j slices the repulsion launcher cuts N rows into — a function of N alone: enough slices for about 1024 workgroups,
+    never more than there are j tiles.  The library refuses any other value."""
+    if n <= 0:
+        return 1
+    nb, jt = -(-n // TSNE_TILE_I), -(-n // TSNE_TILE_J)
+    return max(1, min(-(-_TSNE_TARGET_WG // nb), jt))
+
+
+def knn(x: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """x f32 [N, D] -> (idx int32 [N, k], d2 f32 [N, k]): the k nearest other rows of every row by squared Euclidean distance, exact,
+    ascending by (d2, idx).  D <= 1024, 1 <= k <= 255, k <= N - 1, N <= 2^20."""
+    x = _dev(x, torch.float32, "x").contiguous()
+    if x.dim() != 2:
+        raise ValueError("knn: x must be [N, D]")
+    n, d = x.shape
+    idx = torch.empty((n, max(int(k), 0)), dtype=torch.int32, device=x.device)
+    d2 = torch.empty((n, max(int(k), 0)), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().manner_hip_knn_rows_f32(_ptr(x), n, d, int(k), _ptr(idx), _ptr(d2), _stream()))
+    return idx, d2
+
+
+def tsne_affinities(d2: Tensor, perplexity: float) -> Tuple[Tensor, Tensor]:
+    """d2 f32 [N, k] -> (p [N, k], beta [N]): per row the conditional distribution over its k neighbours whose entropy is
+    log(perplexity) within 1e-5, and the beta the search ended on."""
+    d2 = _dev(d2, torch.float32, "d2").contiguous()
+    n, k = d2.shape
+    p = torch.empty_like(d2)
+    beta = torch.empty((n,), dtype=torch.float32, device=d2.device)
+    with torch.cuda.device(d2.device):
+        _lib.check(_lib.load().manner_hip_tsne_affinities(_ptr(d2), n, k, C.c_float(perplexity), _ptr(p), _ptr(beta), _stream()))
+    return p, beta
+
+
+def tsne_repulsion(y: Tensor, part: Optional[Tensor] = None, zpart: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """y f32 [N, 2] -> (part f32 [split, N, 4], zpart f64 [split * ceil(N / TSNE_TILE_I)]).  part[s, i] = (sum q^2 dx, sum q^2 dy, sum q, 0)
+    of row i over the j rows of slice s, q = 1 / (1 + |y_i - y_j|^2), the self pair (q = 1, force 0) included; Z = zpart.sum() - N."""
+    y = _dev(y, torch.float32, "y").contiguous()
+    n = y.shape[0]
+    s = tsne_j_split(n)
+    if part is None:
+        part = torch.empty((s, n, 4), dtype=torch.float32, device=y.device)
+        zpart = torch.empty((s * -(-n // TSNE_TILE_I),), dtype=torch.float64, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().manner_hip_tsne_repulsion(_ptr(y), n, s, _ptr(part), _ptr(zpart), _stream()))
+    return part, zpart
+
+
+def tsne_step(y: Tensor, part: Tensor, zpart: Tensor, out_idx: Tensor, out_p: Tensor, in_off: Tensor, in_src: Tensor, in_p: Tensor, u: Tensor,
+              gains: Tensor, y_out: Tensor, ypart: Tensor, exaggeration: float, momentum: float, learning_rate: float) -> Tensor:
+    """One iteration from the repulsion sums of ``y``: ``u`` and ``gains`` [N, 2] are updated in place, ``y_out`` (not ``y``) receives the
+    new, centred coordinates; ``ypart`` f64 [2 * ceil(N / TSNE_STEP_ROWS)] is scratch.  Edges: ``out_idx`` int32 / ``out_p`` [N, k] and
+    their transpose ``in_off`` int64 [N + 1] / ``in_src`` int32 / ``in_p``.  Every tensor as the library wants it (contiguous, its dtype):
+    this is called a thousand times per fit and converts nothing."""
+    n, k = out_idx.shape
+    for t, dt, name in ((y, torch.float32, "y"), (part, torch.float32, "part"), (zpart, torch.float64, "zpart"), (out_idx, torch.int32, "out_idx"),
+                        (out_p, torch.float32, "out_p"), (in_off, torch.int64, "in_off"), (in_src, torch.int32, "in_src"), (in_p, torch.float32, "in_p"),
+                        (u, torch.float32, "u"), (gains, torch.float32, "gains"), (y_out, torch.float32, "y_out"), (ypart, torch.float64, "ypart")):
+        if not _dev(t, dt, name).is_contiguous():
+            raise ValueError(f"tsne_step: {name} must be contiguous")
+    s = tsne_j_split(n)
+    if (part.numel() != s * n * 4 or zpart.numel() != s * -(-n // TSNE_TILE_I) or ypart.numel() < 2 * -(-n // TSNE_STEP_ROWS) or in_off.numel() != n + 1
+            or any(t.numel() != 2 * n for t in (y, u, gains, y_out)) or out_p.numel() != n * k or in_p.numel() != in_src.numel()):
+        raise ValueError("tsne_step: buffer sizes do not fit N, k and the split")
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().manner_hip_tsne_step(_ptr(y), _ptr(part), _ptr(zpart), s, _ptr(out_idx), _ptr(out_p), k, _ptr(in_off), _ptr(in_src),
+                                                    _ptr(in_p), in_src.numel(), n, C.c_float(exaggeration), C.c_float(momentum),
+                                                    C.c_float(learning_rate), _ptr(u), _ptr(gains), _ptr(y_out), _ptr(ypart), _stream()))
+    return y_out
+
+
+def tsne_kl(y: Tensor, out_idx: Tensor, out_p: Tensor, zpart: Optional[Tensor] = None) -> Tensor:
+    """Device f64 [1]: KL(P || Q) of the embedding ``y`` [N, 2] over the non-zero entries of the symmetrised P of the directed edges
+    ``out_idx`` / ``out_p`` [N, k].  ``zpart``: that of a repulsion call on the same ``y`` (computed here when None)."""
+    y = _dev(y, torch.float32, "y").contiguous()
+    out_idx = _dev(out_idx, torch.int32, "out_idx").contiguous()
+    out_p = _dev(out_p, torch.float32, "out_p").contiguous()
+    n, k = out_idx.shape
+    if y.numel() != 2 * n or out_p.numel() != n * k:
+        raise ValueError("tsne_kl: y / out_p do not fit out_idx")
+    if zpart is None:
+        zpart = tsne_repulsion(y)[1]
+    s = tsne_j_split(n)
+    if _dev(zpart, torch.float64, "zpart").numel() != s * -(-n // TSNE_TILE_I) or not zpart.is_contiguous():
+        raise ValueError("tsne_kl: zpart does not fit N and the split")
+    klpart = torch.empty((max(-(-n // TSNE_STEP_ROWS), 1),), dtype=torch.float64, device=y.device)
+    kl = torch.zeros((1,), dtype=torch.float64, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().manner_hip_tsne_kl(_ptr(y), _ptr(zpart), s, _ptr(out_idx), _ptr(out_p), k, n, _ptr(klpart), _ptr(kl), _stream()))
+    return kl
