@@ -1,6 +1,7 @@
 """Float64 reference of the encoder and per-slice error maps for the 16-bit attention tests (test_attention_slices_host.py,
-test_gpu_attention_slices.py) and the GEMM tile tests (test_gemm_tiles_host.py, test_gpu_gemm_tiles.py).  A helper module, not a
-conftest.
+test_gpu_attention_slices.py), the GEMM tile tests (test_gemm_tiles_host.py, test_gpu_gemm_tiles.py) and the training step past 4096
+rows and 8192 positions (test_train_scale_host.py, test_gpu_train_scale.py: the full-row objective, the float32 evaluation of the same
+restatement as the yardstick of the fp32 kernels, labels per trip of a row loop and per table row).  A helper module, not a conftest.
 
 ``reference`` restates the oracle's encoder (manner_oracle.encode_tokens / encode_cls_train, whose embedding function it calls)
 in float64, on the operands the 16-bit kernels consume: every weight matrix and embedding table rounded to the mode's 16-bit type
@@ -40,14 +41,14 @@ def limit_threads() -> None:
         torch.set_num_threads(MAX_THREADS)
 
 
-def operands(w: Dict[str, object], mode: Optional[str], device="cpu") -> Dict[str, torch.Tensor]:
-    """The weights as the kernels consume them, in float64: matrices and tables rounded to ``mode``'s 16-bit type first."""
+def operands(w: Dict[str, object], mode: Optional[str], device="cpu", dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    """The weights as the kernels consume them, in ``dtype`` (float64): matrices and tables rounded to ``mode``'s 16-bit type first."""
     out = {}
     for k, v in w.items():
         t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v.detach().cpu()).float()
         if mode is not None and t.dim() == 2:
             t = t.to(DT16[mode]).float()
-        out[k] = t.double().to(device)
+        out[k] = t.to(dtype).to(device)
     return out
 
 
@@ -64,17 +65,41 @@ def _rounder(mode: Optional[str], store: Sequence[str]) -> Callable[[torch.Tenso
     return rnd
 
 
+def embeddings(ids, p, cfg, full: bool = False):
+    """The embedding stage of ``reference``: the oracle's; ``full``: the same sum with HF's padding_idx, which the padded positions
+    of the full-row objective reach — nn.Embedding(padding_idx=pad_token_id) gives the pad token's word row no gradient, and RoBERTa
+    builds its position table the same way (BERT's position table has no padding index)."""
+    if not full:
+        return O.embeddings(ids, p, cfg)
+    pos = O.position_ids(ids, cfg.arch, cfg.pad_id).to(ids.device)
+    x = F.embedding(ids, p["embeddings.word_embeddings.weight"], padding_idx=cfg.pad_id)
+    x = x + p["embeddings.token_type_embeddings.weight"][0]
+    x = x + F.embedding(pos, p["embeddings.position_embeddings.weight"], padding_idx=None if cfg.arch == O.ARCH_BERT else cfg.pad_id)
+    return F.layer_norm(x, (cfg.hidden,), p["embeddings.LayerNorm.weight"], p["embeddings.LayerNorm.bias"], cfg.ln_eps)
+
+
 def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str] = (), train: bool = False, R=None,
-              p_hidden: float = 0.0, p_attn: float = 0.0, p_out: float = 0.0, keep=None, device="cpu", grad_keys=None) -> dict:
+              p_hidden: float = 0.0, p_attn: float = 0.0, p_out: float = 0.0, keep=None, device="cpu", grad_keys=None,
+              dtype=torch.float64, full: bool = False, embed=None) -> dict:
     """Float64 encoder over ``cfg.layers`` layers.
 
     Inference (``train=False``): {"hidden": [hidden_states[0..layers]] each [N, L, H], "cls": [N, H]}.
     Train (``train=True``): the reference of train.encode_train — the dropout sites of manner_oracle.encode_cls_train with
     ``keep(site, kind)`` replaying the kernels' masks — and autograd of (out * R).sum(): {"cls": [N, H], "grads": {name: grad}}
-    over ``grad_keys`` (default: every tensor).  Results are float64 tensors on ``device``."""
+    over ``grad_keys`` (default: every tensor).  Results are float64 tensors on ``device``.
+
+    ``full`` (train mode): the reference of train.encode_full_train — the objective is (hidden_states[-1] * R).sum() with ``R``
+    [N, L, H] over all positions, the padded ones included (computed here as HF computes them: their own queries over the real
+    keys), no [CLS] dropout, the embedding tables with HF's padding_idx (``embeddings``): {"out": [N, L, H], "grads": ...}.
+    ``dtype``: the type the whole restatement is evaluated in — operands, additive mask, ``R`` and every result.  In float32 it is
+    the yardstick of the measured bar of the fp32 kernels (side_ops_ref): run it on the CPU, or on a GPU without TF32.
+    ``embed(ids, p, cfg)`` replaces the embedding stage: the host tests plant defects there."""
     limit_threads()
+    if dtype != torch.float64 and torch.device(device).type == "cuda":
+        assert not torch.backends.cuda.matmul.allow_tf32, "the float32 evaluation is a yardstick only without TF32"
+    assert not full or train, "full rows: the training objective over all positions"
     ids, mask = O._t(ids).long().to(device), O._t(mask).to(device)
-    p = O.bert_named(operands(w, mode, device), cfg)
+    p = O.bert_named(operands(w, mode, device, dtype), cfg)
     if train:
         for k in (p if grad_keys is None else grad_keys):
             p[k].requires_grad_(True)
@@ -87,10 +112,10 @@ def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str
             return x
         return x * keep(site, kind).to(device=device, dtype=x.dtype) / (1.0 - prob)
 
-    add_mask = torch.zeros(mask.shape, dtype=torch.float64, device=device)
+    add_mask = torch.zeros(mask.shape, dtype=dtype, device=device)
     add_mask = add_mask.masked_fill(mask == 0, torch.finfo(torch.float32).min)[:, None, None, :]
     with torch.set_grad_enabled(train):
-        x = drop(O.embeddings(ids, p, cfg), p_hidden, 0, "rows")
+        x = drop(embeddings(ids, p, cfg, full) if embed is None else embed(ids, p, cfg), p_hidden, 0, "rows")
         hidden = [x]
         for l in range(cfg.layers):
             pre = f"encoder.layer.{l}."
@@ -108,11 +133,11 @@ def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str
             x = F.layer_norm(drop(lin(inter, "output.dense"), p_hidden, 8 * (l + 1) + 2, "rows") + x, (h,),
                              p[pre + "output.LayerNorm.weight"], p[pre + "output.LayerNorm.bias"], cfg.ln_eps)
             hidden.append(x)
-        cls = drop(x[:, 0, :], p_out, 1, "cls")
+        cls = x if full else drop(x[:, 0, :], p_out, 1, "cls")
         if not train:
             return {"hidden": hidden, "cls": cls}
-        (cls * O._t(R).to(device=device, dtype=torch.float64)).sum().backward()
-    return {"cls": cls.detach(), "grads": {k: (None if t.grad is None else t.grad) for k, t in p.items() if t.requires_grad}}
+        (cls * O._t(R).to(device=device, dtype=dtype)).sum().backward()
+    return {"out" if full else "cls": cls.detach(), "grads": {k: (None if t.grad is None else t.grad) for k, t in p.items() if t.requires_grad}}
 
 
 # ------------------------------------------------------------------------------------------------ labellings
@@ -161,6 +186,23 @@ def weight_tile_labels(shape, tn: int = 128, tk: int = 64) -> np.ndarray:
 def vector_block_labels(n: int, block: int = 64) -> np.ndarray:
     """A bias or LayerNorm gamma / beta gradient: one slice per ``block`` elements (use with min_count=block, per_slice=True)."""
     return (np.arange(n) // block).astype(np.int64)
+
+
+def trip_labels(mask: np.ndarray, rows_per_trip: int = 4096) -> np.ndarray:
+    """[N, L] int64: packed row // ``rows_per_trip`` over the real tokens, -1 on padding — the trip of a grid-stride row loop that
+    visits the row (ln_bwd_kernel: 1024 workgroups of four waves, one row a wave); for full rows pass a mask of ones."""
+    mask = np.asarray(mask) != 0
+    row = (np.cumsum(mask.ravel()) - 1).reshape(mask.shape)
+    return np.where(mask, row // rows_per_trip, -1).astype(np.int64)
+
+
+def table_row_labels(n_rows: int, rows) -> np.ndarray:
+    """[n_rows, 1] int64: an embedding-table gradient of a batch with repeated ids, one slice per table row in ``rows`` (the label is
+    the row), -1 elsewhere (use with min_count=H, per_slice=True)."""
+    lab = np.full(n_rows, -1, dtype=np.int64)
+    rows = np.asarray(sorted(set(int(r) for r in rows)), dtype=np.int64)
+    lab[rows] = rows
+    return lab[:, None]
 
 
 # ------------------------------------------------------------------------------------------------ the map

@@ -144,17 +144,21 @@ def test_defect_neighbouring_head_dim_case_applied(dh, l0):
         assert min(_measured_excess(case, bad, ("out", "d_x")).values()) >= CLEAR
 
 
-@pytest.mark.parametrize("r,k,o", [(9, 8, 2049), (9, 8, 4100)])
+DX_OC = 1024                    # rows_f32.hip: output features dx_rows_kernel stages per pass
+
+
+@pytest.mark.parametrize("r,k,o", [(9, 8, 2049), (9, 8, 4100), (9, 300, 1030)])
 @pytest.mark.parametrize("defect", ["second_pass_dropped", "stale_dy"])
 def test_defect_in_the_passes_over_O_of_dx(r, k, o, defect):
-    """lin_bwd_x_kernel stages dy in passes of 2048 output features with the accumulators live across the passes"""
+    """dx_rows_kernel (rows_f32.hip) stages dy in passes of DX_OC = 1024 output features with the accumulators live across the passes"""
+    assert (r, k, o) in R.LINEAR_SHAPES and o > DX_OC
     case = R.linear_case(r, k, o, True)
     ref, absolute = case.terms(), case.terms(absolute=True)
     dy, w = case.upstream["y"].double().numpy(), case.leaves["weight"].double().numpy()
-    bad = dy[:, :2048] @ w[:2048]
+    bad = dy[:, :DX_OC] @ w[:DX_OC]
     if defect == "stale_dy":                                     # every later pass multiplies what the first pass staged
-        for o0 in range(2048, o, 2048):
-            no = min(2048, o - o0)
+        for o0 in range(DX_OC, o, DX_OC):
+            no = min(DX_OC, o - o0)
             bad = bad + dy[:, :no] @ w[o0:o0 + no]
     ratio = R.derived_ratio(bad, ref["d_x"][0], absolute["d_x"][0], ref["d_x"][1])
     print(f"{case} d_x, {defect}: planted defect / derived bound = {ratio:.3e}")
