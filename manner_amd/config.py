@@ -80,6 +80,15 @@ PRESETS = {
     "tiny-roberta-514": EncoderConfig(arch=ARCH_ROBERTA, hidden=128, layers=2, heads=2,
                                       intermediate=512, vocab=2048, max_pos=514, type_vocab=1,
                                       ln_eps=1e-5, pad_id=1),
+    # head_dim 32 (inference engine only: eval / validate / test / predict; no training, no full rows, no split modes).
+    # microsoft/MiniLM-L12-H384-uncased — BertModel, 12 heads of 32; Multilingual-MiniLM-L12-H384 and all-MiniLM-L12 share the
+    # shape (a local directory of theirs resolves through from_hf_config with its own vocabulary)
+    "minilm-l12-h384": EncoderConfig(hidden=384, layers=12, heads=12, intermediate=1536, vocab=30522, max_pos=512),
+    # tiny-bert-512 with four heads of 32 where it has two of 64: the head_dim-32 attention kernels at the smallest legal width
+    "tiny-bert-d32": EncoderConfig(hidden=128, layers=2, heads=4, intermediate=512, vocab=2048, max_pos=512),
+    # two MiniLM-shaped layers: the GEMM shapes of H = 384 (N = 1152, 384: multiples of 128 that are not multiples of 256) and six
+    # head pairs per news, without the 12 layers
+    "mini-minilm": EncoderConfig(hidden=384, layers=2, heads=12, intermediate=1536, vocab=2048, max_pos=512),
 }
 
 

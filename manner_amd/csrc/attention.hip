@@ -1099,7 +1099,8 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const T* __restrict__ qcl
 
 int attention_cls(DType dt, const void* qcls, const void* kv, void* ctx_cls, const int32_t* cu, int64_t n_news, int heads,
                   int H, hipStream_t stream) {
-  if (H != heads * 64) return fail(MANNER_HIP_E_INVALID, "head_dim must be 64 (H=%d heads=%d)", H, heads);
+  if (heads > 0 && H == heads * 32) return attention_cls_d32(dt, qcls, kv, ctx_cls, cu, n_news, heads, H, stream);   // attention_d32.hip
+  if (heads <= 0 || H != heads * 64) return fail(MANNER_HIP_E_INVALID, "head_dim %d unsupported (32, 64)", heads > 0 ? H / heads : 0);
   const int64_t pairs = n_news * heads;
   dim3 g((unsigned)((pairs + 3) / 4)), b(256);
   if (dt == DT_BF16)
@@ -1155,7 +1156,11 @@ static int attention_long(DType dt, const void* qkv, void* ctx, const int32_t* c
 
 int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, int64_t n_news, int heads, int H,
                      int max_len, hipStream_t stream, void* split_out, DType split_dt) {
-  if (H != heads * 64) return fail(MANNER_HIP_E_INVALID, "head_dim must be 64 (H=%d heads=%d)", H, heads);
+  if (heads > 0 && H == heads * 32) {                   // attention_d32.hip; no split-operand form there (the x3 modes are refused at create)
+    if (split_out) return fail(MANNER_HIP_E_INVALID, "head_dim 32 has no split-operand attention (use the fp32 mode)");
+    return attention_varlen_d32(dt, qkv, ctx, cu, n_news, heads, H, max_len, stream);
+  }
+  if (heads <= 0 || H != heads * 64) return fail(MANNER_HIP_E_INVALID, "head_dim %d unsupported (32, 64)", heads > 0 ? H / heads : 0);
   if (max_len < 1 || max_len > MANNER_HIP_MAX_LEN_INFER)
     return fail(MANNER_HIP_E_INVALID, "padded length %d outside [1, %d]", max_len, MANNER_HIP_MAX_LEN_INFER);
   const int64_t pairs = n_news * heads;

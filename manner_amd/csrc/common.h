@@ -201,7 +201,8 @@ int gather_cls_rows(DType dt, const void* x, const int32_t* cu, int64_t n_news, 
 int convert_f32_to_16(DType dt, const float* src, void* dst, int64_t n, hipStream_t stream);
 
 // ------------------------------------------------------------------ attention (attention.hip)
-// ctx[tok, head*64 + d] = softmax_k(q.k/8) v over the tokens of the same news; qkv [m, 3H] = [Q|K|V].
+// ctx[tok, head*D + d] = softmax_k(q.k/sqrt(D)) v over the tokens of the same news; qkv [m, 3H] = [Q|K|V]; D = H / heads is 64
+// (the kernels of attention.hip) or 32 (attention_d32.hip), anything else is refused.
 // split_out != NULL (dt == DT_F32, MFMA kernel only): the rows are written as the split operand [hi | hi | lo] of the 16-bit type
 // split_dt, row stride 3H, instead of as f32 ctx rows (x3 modes).
 int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, int64_t n_news, int heads,
@@ -211,6 +212,13 @@ int attention_varlen(DType dt, const void* qkv, void* ctx, const int32_t* cu, in
 // ctx_cls [n_news, H].
 int attention_cls(DType dt, const void* qcls, const void* kv, void* ctx_cls, const int32_t* cu, int64_t n_news,
                   int heads, int H, hipStream_t stream);
+
+// head_dim 32 (attention_d32.hip): what the two entry points above dispatch to when H == 32 heads; one wave (workgroup) per
+// (news, head PAIR), so heads must be even — H % 128 == 0 makes it a multiple of 4.  Inference only, no split-operand output.
+int attention_varlen_d32(DType dt, const void* qkv, void* ctx, const int32_t* cu, int64_t n_news, int heads, int H, int max_len,
+                         hipStream_t stream);
+int attention_cls_d32(DType dt, const void* qcls, const void* kv, void* ctx_cls, const int32_t* cu, int64_t n_news, int heads, int H,
+                      hipStream_t stream);
 
 // ------------------------------------------------------------------ axis-0 attention, fixed head dims (axis0.hip)
 // nn.MultiheadAttention(batch_first=False) core on [N, E, 3D] projections = [q | k | v]: att [N, E, D], attention along axis 0 for each

@@ -443,7 +443,10 @@ int manner_hip_encoder_create(const manner_hip_encoder_config* cfg, const float*
   if (!cfg || !weights || !out) return fail(MANNER_HIP_E_INVALID, "encoder_create: null argument");
   const int H = cfg->hidden, I = cfg->intermediate, L = cfg->layers;
   if (cfg->arch != MANNER_HIP_ARCH_BERT && cfg->arch != MANNER_HIP_ARCH_ROBERTA) return fail(MANNER_HIP_E_INVALID, "encoder_create: unknown arch %d", cfg->arch);
-  if (H <= 0 || H % 128 || H > 1024 || cfg->heads <= 0 || H != cfg->heads * 64) return fail(MANNER_HIP_E_INVALID, "encoder_create: hidden=%d heads=%d (need H %% 128 == 0, H <= 1024, head_dim 64)", H, cfg->heads);
+  // head_dim 64 (attention.hip) or 32 (attention_d32.hip, the MiniLM family); H % 128 == 0 makes the heads of a head_dim-32 model pairs
+  if (H <= 0 || H % 128 || H > 1024 || cfg->heads <= 0 || (H != cfg->heads * 64 && H != cfg->heads * 32)) return fail(MANNER_HIP_E_INVALID, "encoder_create: hidden=%d heads=%d (need H %% 128 == 0, H <= 1024, head_dim 32 or 64)", H, cfg->heads);
+  if (H == cfg->heads * 32 && (precisions & ((1u << MANNER_HIP_PREC_BF16X3) | (1u << MANNER_HIP_PREC_F16X3))))
+    return fail(MANNER_HIP_E_INVALID, "encoder_create: BF16X3 / F16X3 have no head_dim 32 attention (hidden=%d heads=%d); \"fp32\" is the parity-grade mode at head_dim 32", H, cfg->heads);
   if (I <= 0 || I % 128 || L <= 0) return fail(MANNER_HIP_E_INVALID, "encoder_create: intermediate=%d layers=%d unsupported", I, L);
   if (cfg->vocab <= 0 || cfg->max_pos <= 0 || cfg->type_vocab <= 0) return fail(MANNER_HIP_E_INVALID, "encoder_create: bad table sizes");
   if (n_weights != MANNER_HIP_W_EMB_COUNT + L * MANNER_HIP_WL_COUNT) return fail(MANNER_HIP_E_INVALID, "encoder_create: expected %d weight pointers, got %d", MANNER_HIP_W_EMB_COUNT + L * MANNER_HIP_WL_COUNT, n_weights);

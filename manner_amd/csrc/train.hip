@@ -1084,6 +1084,10 @@ void plan_work(Bump& b, Work& w, const manner_hip_encoder_config& c, int64_t Mb)
 int check_cfg(const manner_hip_encoder_config* c, int64_t N, int64_t Lp, int64_t Mb, int32_t precision, int start,
               int max_len = MANNER_HIP_MAX_LEN_TRAIN) {
   if (!c) return fail(MANNER_HIP_E_INVALID, "train: null config");
+  // the inference engine also encodes head_dim 32 (attention_d32.hip); the attention kernels of every entry point that takes a config
+  // (AD above, train_attn.hip) are written for 64.  Refused here, before anything is planned or launched.
+  if (c->heads > 0 && c->hidden == c->heads * 32)
+    return fail(MANNER_HIP_E_INVALID, "head_dim %d: training and full rows support head_dim 64 only", c->hidden / c->heads);
   if (c->hidden % 128 || c->intermediate % 128 || c->hidden / c->heads != AD || c->hidden % c->heads || c->hidden > 64 * LN_MAX ||
       c->layers <= 0 || c->layers > 64)
     return fail(MANNER_HIP_E_INVALID, "train: unsupported architecture H=%d I=%d heads=%d layers=%d", c->hidden, c->intermediate,

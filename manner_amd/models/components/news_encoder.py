@@ -213,6 +213,13 @@ _DATA_PTR = torch.Tensor.data_ptr
 _VERSION = operator.attrgetter("_version")
 
 
+def _require_head_dim_64(cfg, what: str) -> None:
+    """The inference engine encodes head_dim 32 and 64; the training and full-row engines are written for 64.  Raised before any kernel."""
+    if cfg.head_dim != 64:
+        raise ValueError(f"head_dim {cfg.head_dim} (hidden={cfg.hidden}, heads={cfg.heads}): {what} supports head_dim 64 only — "
+                         f"at head_dim 32 the inference engine serves eval() without a graph (validate / test / predict), fit does not run yet")
+
+
 class MannerTextEncoder(nn.Module):
     """reference news_encoder.py:11-37."""
 
@@ -220,7 +227,8 @@ class MannerTextEncoder(nn.Module):
     #: under fp16 autocast (Lightning `precision: 16-mixed`, the shipped configs/trainer/default.yaml:12) "f16" — the MFMA path on
     #: IEEE half; under bf16 autocast (`bf16-mixed`) "bf16"; outside autocast (`trainer.precision=32`) the parity-grade mode
     #: "f16x3" (f32 activations, split-operand f16 GEMMs with f32 accumulation: within 1e-4 of the reference's fp32 path, ranking
-    #: indices as the oracle's).  A string pins one mode whatever the caller's state ("f16", "bf16", "fp32" = f32 MFMA, "f16x3",
+    #: indices as the oracle's; "fp32" where the split modes do not apply: hidden / intermediate size not a multiple of 256, or
+    #: head_dim 32).  A string pins one mode whatever the caller's state ("f16", "bf16", "fp32" = f32 MFMA, "f16x3",
     #: "bf16x3"); the environment variable MANNER_HIP_PRECISION pins it for a whole process (A/B runs).
     precision: Optional[str] = os.environ.get("MANNER_HIP_PRECISION") or None
 
@@ -232,6 +240,8 @@ class MannerTextEncoder(nn.Module):
         if ac is not None:
             return ac
         cfg = self.plm_model.cfg                       # the split-operand GEMMs tile K in 256s: tiny test models take the f32 MFMA mode
+        if cfg.head_dim == 32:                         # the split modes have no head_dim-32 attention (MiniLM): "fp32" whatever H is
+            return "fp32"
         return "f16x3" if cfg.hidden % 256 == 0 and cfg.intermediate % 256 == 0 else "fp32"
 
     def resolved_train_precision(self) -> str:
@@ -375,6 +385,7 @@ class MannerTextEncoder(nn.Module):
         reference's default); with the embeddings frozen too, the frozen prefix runs once on the inference engine.
         ``dropout=False``: the same differentiable engine with every dropout off (eval() with grad mode on)."""
         plm = self.plm_model
+        _require_head_dim_64(plm.cfg, "train() (or eval() with a graph)")
         tp = self.resolved_train_precision()
         params = {k: v for k, v in self._plm_params().items() if not k.startswith("pooler.")}
         emb_frozen = not any(p.requires_grad for k, p in params.items() if k.startswith("embeddings."))
@@ -837,6 +848,7 @@ class PLMTextEncoder(nn.Module):
         ids, mask = tokenized_text["input_ids"], tokenized_text["attention_mask"]
         if not ids.is_cuda:
             raise RuntimeError("PLMTextEncoder.forward needs GPU tensors — the HIP path has no CPU fallback")
+        _require_head_dim_64(self.plm_model.cfg, "PLMTextEncoder's full rows (train() and eval())")
         if self.training or _wants_graph(self):
             # train() mode (news_encoder.py:160-171; trained by baselines/nrms_plm_module.py:119-135): the PLM with HF's dropouts and
             # autograd over "full rows" (padded positions included), dropout, the axis-0 attention, dropout, the pooler — every

@@ -1,0 +1,66 @@
+"""Shared by tests/test_d32_host.py and tests/test_gpu_d32.py: the head_dim-32 fixtures and the two planted defects.
+
+Both defects are applied THROUGH THE WEIGHTS, so the oracle (and the engine) under test stays unchanged:
+  scale    the head_dim-64 softmax constant left in place: scores * 0.125 where 32^-0.5 belongs.  q.k is bilinear in the query
+           projection, so scaling query.weight and query.bias by 0.125 / 32^-0.5 gives exactly that.
+  crossed  the two heads of a pair crossed in the second product: head h is given head h^1's V, i.e. the rows (output features) of
+           value.weight / value.bias permuted in blocks of 32.
+"""
+import json
+import os
+
+import numpy as np
+
+from manner_amd.config import PRESETS
+from manner_amd.weights import make_plm_weights
+
+FP32_TOL = 1e-4                     # the project's fp32 bar
+ORACLE_TOL = 2e-5                   # the bar tests/test_oracle_golden.py holds the oracle to
+D32_LENGTHS = [2, 3, 31, 32, 33, 64, 65, 96, 127, 128, 129, 160, 161, 256, 257, 512]
+GOLDEN_ENC = ["enc_tiny_bert_d32", "enc_mini_minilm"]
+GOLDEN_ENC_16BIT = ["enc_tiny_bert_d32_s10", "enc_mini_minilm_s10"]     # the same tokens and seeds at std 0.1 (see meta["std_note"])
+TWIN_PRESET = "tiny-bert-512"       # tiny-bert-d32 with two heads of 64: the head_dim-64 kernels on the same seed, std and tokens
+
+
+def twin_config(cfg):
+    """The head_dim-64 twin of a head_dim-32 shape: half the heads, everything else equal ("tiny-bert-d32" -> "tiny-bert-512")."""
+    import dataclasses
+    return dataclasses.replace(cfg, heads=cfg.heads // 2)
+
+
+def load(golden_dir, name):
+    z = np.load(os.path.join(golden_dir, name + ".npz"))
+    return z, json.loads(str(z["meta"]))
+
+
+def fixture_weights(meta, std=None):
+    cfg = PRESETS[meta["preset"]]
+    return cfg, make_plm_weights(cfg, seed=meta["seed"], std=meta["std"] if std is None else std)
+
+
+def defect_scale(cfg, w):
+    f = np.float32(0.125 / 32 ** -0.5)
+    out = {k: v.copy() for k, v in w.items()}
+    for layer in range(cfg.layers):
+        p = f"encoder.layer.{layer}.attention.self.query."
+        out[p + "weight"] = (w[p + "weight"] * f).astype(np.float32)
+        out[p + "bias"] = (w[p + "bias"] * f).astype(np.float32)
+    return out
+
+
+def defect_crossed(cfg, w):
+    assert cfg.head_dim == 32 and cfg.heads % 2 == 0
+    rows = np.arange(cfg.hidden).reshape(cfg.heads // 2, 2, 32)[:, ::-1].reshape(-1)      # feature block of head h <- head h ^ 1
+    out = {k: v.copy() for k, v in w.items()}
+    for layer in range(cfg.layers):
+        p = f"encoder.layer.{layer}.attention.self.value."
+        out[p + "weight"] = np.ascontiguousarray(w[p + "weight"][rows])
+        out[p + "bias"] = np.ascontiguousarray(w[p + "bias"][rows])
+    return out
+
+
+DEFECTS = {"scale": defect_scale, "crossed": defect_crossed}
+
+
+def cosine(a, b):
+    return (a * b).sum(1) / np.linalg.norm(a, axis=1) / np.linalg.norm(b, axis=1)
