@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from manner_amd.config import PRESETS
+from manner_amd.config import PRESETS, EncoderConfig
 from manner_amd.weights import make_plm_weights
 
 FP32_TOL = 1e-4                     # the project's fp32 bar
@@ -48,11 +48,12 @@ def defect_scale(cfg, w):
     return out
 
 
-def defect_crossed(cfg, w):
+def defect_crossed(cfg, w, layers=None):
+    """``layers``: the layers whose attention is crossed (default: all of them)."""
     assert cfg.head_dim == 32 and cfg.heads % 2 == 0
     rows = np.arange(cfg.hidden).reshape(cfg.heads // 2, 2, 32)[:, ::-1].reshape(-1)      # feature block of head h <- head h ^ 1
     out = {k: v.copy() for k, v in w.items()}
-    for layer in range(cfg.layers):
+    for layer in (range(cfg.layers) if layers is None else layers):
         p = f"encoder.layer.{layer}.attention.self.value."
         out[p + "weight"] = np.ascontiguousarray(w[p + "weight"][rows])
         out[p + "bias"] = np.ascontiguousarray(w[p + "bias"][rows])
@@ -60,6 +61,55 @@ def defect_crossed(cfg, w):
 
 
 DEFECTS = {"scale": defect_scale, "crossed": defect_crossed}
+
+
+# the stress cases of tests/test_gpu_long_rows.py at head_dim 32: layer 0 runs the long flash kernel, the last layer the [CLS] branch
+STRESS_CFG = EncoderConfig(hidden=256, heads=8, layers=2, intermediate=1024, vocab=2048, max_pos=512)
+MARKER_ID = 7                       # the token whose embedding the peaked sets rank the keys by
+MARKER_AT = {"peaked_last": lambda ln: ln - 1, "peaked_first": lambda ln: 1}
+
+
+def stress_weights(kind, seed=80, cfg=STRESS_CFG, with_pooler=True):
+    """"equal": q = 0, every score 0, the softmax uniform over the row.  "peaked_first" / "peaked_last" (the same weights; the kind says
+    where the caller puts the marker token, MARKER_AT): rank-one scores per head of ``cfg.head_dim`` — q = a (u.x + b) u and
+    k = a u u^T x in the head's first feature, so every query ranks the keys by u.x, largest at the marker token, whose (normalised)
+    embedding is u, and the softmax is close to one-hot there.  The twin of a head_dim-32 shape (twin_config) takes the same
+    construction with its heads of 64."""
+    w = make_plm_weights(cfg, seed=seed, std=0.05, with_pooler=with_pooler)
+    H, d = cfg.hidden, cfg.head_dim
+    w["embeddings.position_embeddings.weight"][:] = 0.0
+    w["embeddings.token_type_embeddings.weight"][:] = 0.0
+    g = np.random.default_rng(seed)
+    for layer in range(cfg.layers):
+        p = f"encoder.layer.{layer}.attention.self."
+        if kind == "equal":
+            w[p + "query.weight"][:] = 0.0
+            w[p + "query.bias"][:] = 0.0
+        else:
+            u = g.standard_normal(H).astype(np.float32)
+            u -= u.mean()
+            u /= np.linalg.norm(u)
+            a = 6.0
+            wq = np.zeros((H, H), np.float32)
+            wk = np.zeros((H, H), np.float32)
+            for h in range(cfg.heads):
+                wq[d * h] = a * u
+                wk[d * h] = a * u
+            w[p + "query.weight"][:] = wq
+            w[p + "key.weight"][:] = wk
+            w[p + "query.bias"][:] = 0.0
+            w[p + "query.bias"][0::d] = a * 4.0
+            w[p + "key.bias"][:] = 0.0
+            if layer == 0:
+                w["embeddings.word_embeddings.weight"][MARKER_ID] = u * 40.0
+    return cfg, w
+
+
+def place_marker(ids, lengths, kind):
+    """The marker token of a peaked set at MARKER_AT[kind] of every news (in place)."""
+    for n, ln in enumerate(lengths):
+        ids[n, MARKER_AT[kind](int(ln))] = MARKER_ID
+    return ids
 
 
 def cosine(a, b):

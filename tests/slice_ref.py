@@ -80,7 +80,7 @@ def embeddings(ids, p, cfg, full: bool = False):
 
 def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str] = (), train: bool = False, R=None,
               p_hidden: float = 0.0, p_attn: float = 0.0, p_out: float = 0.0, keep=None, device="cpu", grad_keys=None,
-              dtype=torch.float64, full: bool = False, embed=None) -> dict:
+              dtype=torch.float64, full: bool = False, embed=None, attn=None) -> dict:
     """Float64 encoder over ``cfg.layers`` layers.
 
     Inference (``train=False``): {"hidden": [hidden_states[0..layers]] each [N, L, H], "cls": [N, H]}.
@@ -93,7 +93,10 @@ def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str
     keys), no [CLS] dropout, the embedding tables with HF's padding_idx (``embeddings``): {"out": [N, L, H], "grads": ...}.
     ``dtype``: the type the whole restatement is evaluated in — operands, additive mask, ``R`` and every result.  In float32 it is
     the yardstick of the measured bar of the fp32 kernels (side_ops_ref): run it on the CPU, or on a GPU without TF32.
-    ``embed(ids, p, cfg)`` replaces the embedding stage: the host tests plant defects there."""
+    ``embed(ids, p, cfg)`` replaces the embedding stage: the host tests plant defects there.  ``attn(layer, q, k, v, add_mask)`` replaces
+    the score, softmax and PV stage of a layer (q, k, v [N, heads, L, head_dim] after their storage point, add_mask [N, 1, 1, L]; it
+    returns the context [N, heads, L, head_dim] before the "ctx" point and rounds the "probs" point itself): test_d32_slices_host.py
+    plants one defect per loop of attention_d32.hip there."""
     limit_threads()
     if dtype != torch.float64 and torch.device(device).type == "cuda":
         assert not torch.backends.cuda.matmul.allow_tf32, "the float32 evaluation is a yardstick only without TF32"
@@ -124,9 +127,14 @@ def reference(cfg, w, ids, mask, mode: Optional[str] = None, store: Sequence[str
                 return F.linear(t, p[pre + name + ".weight"], p[pre + name + ".bias"])
 
             q, k, v = (rnd(lin(x, f"attention.self.{m}"), "qkv").view(n, s, a, d).transpose(1, 2) for m in ("query", "key", "value"))
-            att = F.softmax(torch.matmul(q, k.transpose(2, 3)) * (d ** -0.5) + add_mask, dim=-1)
-            att = rnd(drop(att, p_attn, 8 * (l + 1), "attn"), "probs")
-            ctx = rnd(torch.matmul(att, v).transpose(1, 2).reshape(n, s, h), "ctx")
+            if attn is None:
+                att = F.softmax(torch.matmul(q, k.transpose(2, 3)) * (d ** -0.5) + add_mask, dim=-1)
+                att = rnd(drop(att, p_attn, 8 * (l + 1), "attn"), "probs")
+                ctx = torch.matmul(att, v)
+            else:
+                assert not train, "the attention hook restates the inference kernels"
+                ctx = attn(l, q, k, v, add_mask)
+            ctx = rnd(ctx.transpose(1, 2).reshape(n, s, h), "ctx")
             x = F.layer_norm(drop(lin(ctx, "attention.output.dense"), p_hidden, 8 * (l + 1) + 1, "rows") + x, (h,),
                              p[pre + "attention.output.LayerNorm.weight"], p[pre + "attention.output.LayerNorm.bias"], cfg.ln_eps)
             inter = rnd(F.gelu(lin(x, "intermediate.dense")), "inter")

@@ -89,42 +89,9 @@ def test_fp32_encode_hidden_of_long_rows_matches_reference(golden_dir, measured)
         assert err < D.FP32_TOL, (k, err)
 
 
-# the stress cases of tests/test_gpu_long_rows.py with stride 32: layer 0 runs the long flash kernel, the last layer the [CLS] branch
-STRESS_CFG = EncoderConfig(hidden=256, heads=8, layers=2, intermediate=1024, vocab=2048, max_pos=512)
-
-
-def _stress_weights(kind, seed=80):
-    cfg = STRESS_CFG
-    w = make_plm_weights(cfg, seed=seed, std=0.05)
-    H = cfg.hidden
-    w["embeddings.position_embeddings.weight"][:] = 0.0
-    w["embeddings.token_type_embeddings.weight"][:] = 0.0
-    g = np.random.default_rng(seed)
-    for layer in range(cfg.layers):
-        p = f"encoder.layer.{layer}.attention.self."
-        if kind == "equal":                              # q = 0: every score 0, the softmax uniform over the row
-            w[p + "query.weight"][:] = 0.0
-            w[p + "query.bias"][:] = 0.0
-        else:
-            # rank-one scores per head of 32: q = a (u.x + b) u and k = a u u^T x, so every query ranks the keys by u.x — largest at
-            # the marker token, whose (normalised) embedding is u — and the softmax is close to one-hot there
-            u = g.standard_normal(H).astype(np.float32)
-            u -= u.mean()
-            u /= np.linalg.norm(u)
-            a = 6.0
-            wq = np.zeros((H, H), np.float32)
-            wk = np.zeros((H, H), np.float32)
-            for h in range(cfg.heads):
-                wq[32 * h] = a * u
-                wk[32 * h] = a * u
-            w[p + "query.weight"][:] = wq
-            w[p + "key.weight"][:] = wk
-            w[p + "query.bias"][:] = 0.0
-            w[p + "query.bias"][0::32] = a * 4.0
-            w[p + "key.bias"][:] = 0.0
-            if layer == 0:
-                w["embeddings.word_embeddings.weight"][7] = u * 40.0
-    return cfg, w
+# the stress cases of tests/test_gpu_long_rows.py with stride 32 (d32_common.stress_weights, shared with test_gpu_d32_slices.py)
+STRESS_CFG = D.STRESS_CFG
+_stress_weights = D.stress_weights
 
 
 @pytest.mark.parametrize("kind", ["equal", "peaked_last", "peaked_first"])
@@ -132,10 +99,8 @@ def test_fp32_long_kernels_match_the_oracle_under_stress(kind, measured):
     cfg, w = _stress_weights(kind)
     lengths = [129, 160, 161, 512, 2, 128]
     ids, mask = synth_news_tokens(len(lengths), cfg, seed=81, lengths=np.asarray(lengths))
-    marker = {"peaked_last": lambda ln: ln - 1, "peaked_first": lambda ln: 1}.get(kind)
-    if marker is not None:
-        for n, ln in enumerate(lengths):
-            ids[n, marker(ln)] = 7
+    if kind in D.MARKER_AT:
+        D.place_marker(ids, lengths, kind)
     enc = hip.HipEncoder(cfg, w, precisions=("fp32",), device=DEV)
     try:
         out = enc.encode_cls(_cuda(ids), _cuda(mask), precision="fp32", host_lengths=mask.sum(1)).cpu().numpy()
